@@ -5,7 +5,7 @@ One "step" = one V-cycle of the hot path (`ldiv!` semantics of preconditioner.jl
 one `__solve!`, multilevel.jl:214-239) over the whole 16.7 M-unknown system, on the hierarchy
 built by `ruge_stuben` defaults (symmetric Gauss-Seidel pre/post), with b already resident in HBM.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--size 256]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--size 256] [--dump-outputs DIR]
     python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...   (N > 1, a launcher's RANK / WORLD_SIZE)
     python bench.py --gpus N ...        (N > 1, no launcher: bench.py spawns its N ranks itself, `self_launch`)
 
@@ -50,6 +50,31 @@ def vcycle_bytes(ml, sweeps_per_level):
         total += spmv_bytes(lev.P.nnz, n, nc) + 8 * n
     total += 8 * ml.final_A.m ** 2
     return total
+
+
+DUMP_FULL_MAX = 1 << 22     # --dump-outputs: a solution of up to 4 Mi entries is written whole (32 MiB of float64)
+DUMP_SAMPLE = 1 << 21       # larger ones as a fixed sample: 2 Mi values + their indices, float64 (32 MiB)
+DUMP_SEED = 20251015
+
+
+def dump_outputs(outdir, z):
+    """--dump-outputs DIR: what the timed path returned in its last step — the solution z of one V-cycle (ldiv!) — as float64
+    .npy files, at most 64 MB in all, so that two builds run with the same arguments can be compared output for output:
+      z.npy                          the whole vector, when it has at most DUMP_FULL_MAX entries, otherwise
+      z_sample.npy, z_sample_index.npy   z at DUMP_SAMPLE indices drawn without replacement by a fixed seed (sorted; the
+                                     indices stored as float64, exact below 2^53)
+      z_summary.npy                  [n, ||z||_2, ||z||_inf, sum(z)] of the whole vector"""
+    z = np.ascontiguousarray(z, dtype=np.float64)
+    n = z.shape[0]
+    os.makedirs(outdir, exist_ok=True)
+    if n <= DUMP_FULL_MAX:
+        np.save(os.path.join(outdir, "z.npy"), z)
+    else:
+        idx = np.sort(np.random.Generator(np.random.PCG64(DUMP_SEED)).choice(n, DUMP_SAMPLE, replace=False))
+        np.save(os.path.join(outdir, "z_sample.npy"), z[idx])
+        np.save(os.path.join(outdir, "z_sample_index.npy"), idx.astype(np.float64))
+    np.save(os.path.join(outdir, "z_summary.npy"),
+            np.array([n, np.linalg.norm(z), np.abs(z).max(initial=0.0), z.sum()], dtype=np.float64))
 
 
 def pmc_traffic(N, enabled=True):
@@ -351,7 +376,12 @@ def main():
                          "memory over the shared-memory transport, checked against the oracle — functional, never a measurement")
     ap.add_argument("--no-overlap", action="store_true",
                     help="with --setup gpu: build the HBM hierarchy after ruge_stuben instead of level by level beside it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the solution of the last timed V-cycle to DIR/*.npy (float64, <= 64 MB: "
+                         "a fixed seeded sample of a larger vector; dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "RANK" not in os.environ and "WORLD_SIZE" not in os.environ:
         return self_launch(args.gpus)   # started the way `--gpus 1` is started: no launcher — be the launcher
@@ -419,6 +449,8 @@ def main():
     ms_per_step = 1e3 * elapsed / args.steps
     value = n * args.steps / elapsed
     z_timed = zd.download()      # what the LAST timed V-cycle produced (checked against the oracle below)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, z_timed)
 
     # dominant kernel of the metric: the fine-level CSR SpMV, timed with HIP events on its own stream
     spmv_ms = dev.bench_op(0, 0, reps=50, warmup=5)

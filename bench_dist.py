@@ -287,7 +287,7 @@ def main_distributed(args):
     host_barrier()
     import amg_amd as AMG
     from amg_amd import sharded as SH
-    from bench import cpu_baseline, spmv_bytes, uniform
+    from bench import cpu_baseline, dump_outputs, spmv_bytes, uniform
 
     host_exec = bool(getattr(args, "host_exec", False))   # launcher self-test without GPUs: amgh_dist_* executed in host memory
     one_gpu = os.environ.get("AMG_DIST_ONE_GPU") == "1"   # functional check on a single-GPU box: every rank on device 0
@@ -496,6 +496,8 @@ def main_distributed(args):
             res["tail_ms"] = run.tail_ms()               # (the owner of the collapsed levels only; the others wait below)
         z = assemble_on_rank0(ctx, label, z_loc)
         if rank == 0:
+            if label == "primary" and getattr(args, "dump_outputs", None):
+                dump_outputs(args.dump_outputs, z)      # (--dump-outputs: the timed path's result, the ranks' rows assembled)
             res["parity"] = check_parity(ctx, ml_k, b, z, kind, gs_mode)
         res["gs_mode"] = gs_mode if kind == "gs" else None
         res["sharded_levels"] = len(lv)

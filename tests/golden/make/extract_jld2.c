@@ -2,7 +2,7 @@
  * reference's JLD2 (HDF5) test fixtures as plain text, so that
  * make_fixtures.py can store them as .npz DATA fixtures.
  *
- *   gcc extract_jld2.c -I/opt/conda/include -L/opt/conda/lib -lhdf5 -o extract_jld2
+ *   gcc extract_jld2.c [-I$HDF5_DIR/include -L$HDF5_DIR/lib] -lhdf5 -o extract_jld2
  *   ./extract_jld2 file.jld2 sparse A     -> m n nnz / colptr / rowval / nzval (1-based as stored)
  *   ./extract_jld2 file.jld2 dense  B     -> ndims dims / values (HDF5 row-major = Julia column-major reversed)
  */

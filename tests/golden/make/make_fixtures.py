@@ -1,15 +1,15 @@
 #!/usr/bin/env python3
 """Generate tests/golden/*.npz from the DATA fixtures the reference's own tests hold.
 
-Run in the build container only (needs /root/reference and, for the two JLD2
-files, libhdf5 from /opt/conda).  The outputs are data — sparse-matrix arrays,
+Needs a checkout of the reference (AlgebraicMultigrid.jl) and, for the two JLD2
+files, libhdf5 (HDF5_DIR: its install prefix, if not on the default paths).  The outputs are data — sparse-matrix arrays,
 dense vectors and the known-answer vectors quoted in the reference's tests —
 never source text.  Everything is stored 0-based, CSC (colptr/rowval/nzval), as
 the reference holds its matrices.
 
-    python tests/golden/make/make_fixtures.py
+    python tests/golden/make/make_fixtures.py REFERENCE_CHECKOUT
 
-Sources (relative to /root/reference/test):
+Sources (relative to the reference's test/):
   thing.jl randlap.jl test.jl ref_S_test.jl ref_R.jl onetoall.jl   one-line CSC literals
   ref_split_test.txt                                               expected C/F vector
   bug.jld2 (G)  lin_elastic_2d.jld2 (A, b, B)                      HDF5
@@ -19,10 +19,11 @@ import os
 import re
 import subprocess
 import sys
+import tempfile
 
 import numpy as np
 
-REF = "/root/reference/test"
+REF = None   # the reference checkout's test/ directory (main)
 HERE = os.path.dirname(os.path.abspath(__file__))
 OUT = os.path.dirname(HERE)
 
@@ -43,10 +44,11 @@ def parse_jl_csc(path):
 
 
 def build_extractor():
-    exe = "/tmp/extract_jld2"
-    subprocess.check_call(
-        ["gcc", os.path.join(HERE, "extract_jld2.c"), "-I/opt/conda/include", "-L/opt/conda/lib",
-         "-Wl,-rpath,/opt/conda/lib", "-lhdf5", "-o", exe])
+    exe = os.path.join(tempfile.mkdtemp(), "extract_jld2")
+    hdf5 = os.environ.get("HDF5_DIR")
+    flags = ["-I" + os.path.join(hdf5, "include"), "-L" + os.path.join(hdf5, "lib"),
+             "-Wl,-rpath," + os.path.join(hdf5, "lib")] if hdf5 else []
+    subprocess.check_call(["gcc", os.path.join(HERE, "extract_jld2.c")] + flags + ["-lhdf5", "-o", exe])
     return exe
 
 
@@ -83,6 +85,10 @@ def golden_vectors():
 
 
 def main():
+    global REF
+    if len(sys.argv) != 2:
+        raise SystemExit("usage: make_fixtures.py REFERENCE_CHECKOUT")
+    REF = os.path.join(sys.argv[1], "test")
     for nm in ["thing", "randlap", "test", "ref_S_test", "ref_R", "onetoall"]:
         np.savez_compressed(os.path.join(OUT, nm + ".npz"), **parse_jl_csc(os.path.join(REF, nm + ".jl")))
     split = np.loadtxt(os.path.join(REF, "ref_split_test.txt")).astype(np.int32)

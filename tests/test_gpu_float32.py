@@ -253,10 +253,10 @@ def test_float32_gauss_seidel_pipelined_across_the_ranks():
     assert rel(out["exact"], xo) <= F32_TOL
     if serialized:
         # (the library re-creates the ranks' sweep streams in rank order and probes again, three times, before it settles for turns:
-        # with the 8 hardware queues tests/conftest.py asks for, 2-4 virtual ranks must end up side by side)
+        # with 8 or more hardware queues in the environment, 2-4 virtual ranks must end up side by side)
         msg = "the virtual ranks' streams shared a hardware queue in this process: swept in turns (oracle parity held)"
-        if os.environ.get("GPU_MAX_HW_QUEUES") == "8":
-            pytest.fail(msg + " although GPU_MAX_HW_QUEUES=8 was requested and the streams were re-created: the pipelined sweep did not run")
+        if int(os.environ.get("GPU_MAX_HW_QUEUES") or 0) >= 8:
+            pytest.fail(msg + " although 8 or more hardware queues were available and the streams were re-created: the pipelined sweep did not run")
         pytest.skip(msg)
 
 

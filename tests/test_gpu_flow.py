@@ -1,7 +1,7 @@
 """The wavefront of blocks as a DATAFLOW (csrc/hip/gs_flow.hpp): rows published into mailboxes the moment they are
 computed, blocks starting on finished faces, the packed rows streamed straight into registers.  Same plan, same
 arithmetic as the chained and launched sweeps of gs_blocks.hpp — and so the scalar lexicographic loop of
-/root/reference/src/smoother.jl:61-90 (gs!) and :193-221 (sor_step!) BIT FOR BIT: against the oracle's loops, against
+the reference's src/smoother.jl:61-90 (gs!) and :193-221 (sor_step!) BIT FOR BIT: against the oracle's loops, against
 the host execution of the plan (amgh_debug_bw_sweep_host), against the two other executions on the device.  Plus what a
 protocol built on polling owes its callers: a wait that gives up is an error code, never numbers (a forced protocol
 error), and a soak under memory load, eager and graph-replayed."""
@@ -244,7 +244,7 @@ def test_a_forced_protocol_error_is_an_error_code_not_numbers():
 @pytest.mark.parametrize("case,bs", [("poisson", 8), ("poisson", 3), ("poisson", 5), ("galerkin", 4), ("galerkin", 7), ("galerkin", 2),
                                      ("poisson-sor", 4), ("galerkin-sor", 3), ("poisson", 33)])
 def test_blocks_of_right_hand_sides_on_the_dataflow_layout_equal_the_single_columns_bit_for_bit(case, bs):
-    """bs > 1 (`MultiLevelWorkspace{TX,bs}`, /root/reference/src/multilevel.jl:28-59; the reference loops the columns inside
+    """bs > 1 (`MultiLevelWorkspace{TX,bs}`, the reference's src/multilevel.jl:28-59; the reference loops the columns inside
     gs!, smoother.jl:77): ONE launch sweeps all columns, a workgroup taking one block for a group of up to 4 (7-point rows) /
     3 (longer rows) columns — a walker wave, an LDS x and a set of mailboxes per column, one fetcher wave for the group,
     every walker streaming the same records; odd block sizes leave walkers of the last group idle.  Per column the

@@ -197,7 +197,7 @@ def test_c4_256cubed_row_sharded_gauss_seidel_matches_the_frozen_halo_emulation_
 def test_c4_256cubed_row_sharded_exact_gauss_seidel_is_the_oracle_cycle(c3):
     """Config C4 with the library's default across shards — lexicographic Gauss-Seidel over the whole level, the ranks
     sweeping in turn: one V-cycle of the default hierarchy on 2 and 4 shards IS the single-process oracle's cycle at the
-    north-star tolerance (/root/reference/src/smoother.jl:61-90, multilevel.jl:214-239)."""
+    north-star tolerance (the reference's src/smoother.jl:61-90, multilevel.jl:214-239)."""
     A, ml = c3
     b = uniform(A.m, 0)
     want = O.OracleHierarchy(ml).precond(b)

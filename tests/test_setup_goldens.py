@@ -1,5 +1,5 @@
 """Host setup phase (libamgsetup) against the known-answer tests of the reference
-(/root/reference/test/runtests.jl, sa_tests.jl, test_regression.jl, nns_test.jl)."""
+(the reference's test/runtests.jl, sa_tests.jl, test_regression.jl, nns_test.jl)."""
 import numpy as np
 import pytest
 import scipy.sparse as sp

@@ -1,5 +1,6 @@
 import gc, os, sys
-sys.path.insert(0, "/root/repo")
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
 import amg_amd as AMG
 from amg_amd.device import DeviceHierarchy
 N = 256

@@ -1,6 +1,7 @@
 // Which hardware queue does the runtime give a new stream?  Pairs of streams are tested for concurrency with the flag exchange of
 // dist_pipe_probe (amghip_dist.hpp): two streams on one hardware queue run their kernels one after the other.
-//   hipcc --offload-arch=gfx950 -O2 tools/hwq_probe.hip -o tools/hwq_probe && GPU_MAX_HW_QUEUES=8 tools/hwq_probe
+//   hipcc --offload-arch=gfx950 -O2 tools/hwq_probe.hip -o tools/hwq_probe && tools/hwq_probe
+//   (with the hardware queues the environment gives the process)
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <vector>

@@ -1,11 +1,12 @@
 """amgh_pcg: one launch per operation against the fused recurrence (tunable pcg_fused), C5 and Poisson grids."""
 import os, sys, time
 import numpy as np
-sys.path.insert(0, "/root/repo")
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
 import amg_amd as AMG
 from bench import uniform
 lib = AMG.hip_lib()
-d = np.load("/root/repo/tests/golden/lin_elastic_2d.npz")
+d = np.load(os.path.join(ROOT, "tests", "golden", "lin_elastic_2d.npz"))
 A = AMG.SparseMatrixCSC.from_arrays(int(d["m"]), int(d["n"]), d["colptr"], d["rowval"], d["nzval"])
 ml = AMG.smoothed_aggregation(A, B=d["B"])
 def t_cg(A, b, ml, reps=20, **kw):

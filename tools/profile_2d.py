@@ -1,6 +1,7 @@
 import os, sys, time
 os.environ["AMGH_VERBOSE"]="1"
-sys.path.insert(0, "/root/repo")
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
 import numpy as np
 import amg_amd as AMG
 A = AMG.poisson((4096, 4096))
