@@ -10,6 +10,7 @@ The directory name contains a dot, so import it through the repo-root alias:
     ml = AMG.ruge_stuben(A)
     x  = AMG._solve(ml, A @ np.ones(A.m))
     p  = AMG.aspreconditioner(ml); x = AMG.cg(A, b, Pl=p)
+    x  = AMG.gmres(M, b, Pl=AMG.aspreconditioner(AMG.ruge_stuben(M, symmetry=AMG.NoSymmetry())))
 """
 from ._libs import AMGError, gpu_available, hip_lib, setup_lib  # noqa: F401
 from .sparse import SparseMatrixCSC  # noqa: F401
@@ -22,7 +23,7 @@ from .hierarchy import (Classical, DenseLUFactorization, HermitianSymmetry, Jaco
                         ruge_stuben, smoothed_aggregation)
 from .solve import (AMGSolver, F, Identity, Preconditioner, RugeStubenAMG, RugeStubenPreconBuilder,  # noqa: F401
                     SmoothedAggregationAMG, SmoothedAggregationPreconBuilder, V, W, _solve, _solve_inplace,
-                    aspreconditioner, cg, init, solve, solve_)
+                    aspreconditioner, cg, gmres, init, solve, solve_)
 from .device import DeviceBuffer, DeviceCSR, DeviceHierarchy  # noqa: F401
 from . import sharded  # noqa: F401
 

@@ -138,6 +138,10 @@ def _bind_solve_phase(L, creal, coarse_fn):
     pcg_args = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, vp, C.POINTER(C.c_int)]
     L.amgh_pcg.argtypes = pcg_args
     L.amgh_pcg_d.argtypes = pcg_args
+    gmres_args = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, vp, C.POINTER(C.c_int)]
+    L.amgh_gmres.argtypes = gmres_args
+    L.amgh_gmres_d.argtypes = gmres_args
+    L.amgh_debug_gmres_reorth.argtypes = [vp]
     L.amgh_level_spmv.argtypes = [vp, C.c_int, C.c_int, vp, vp]
     L.amgh_level_spmv_d.argtypes = [vp, C.c_int, C.c_int, vp, vp]
     L.amgh_level_residual_d.argtypes = [vp, C.c_int, vp, vp, vp]

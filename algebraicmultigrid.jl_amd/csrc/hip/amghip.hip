@@ -14,6 +14,7 @@
 #include "amghip_internal.hpp"
 #include "gs_schedule.hpp"
 #include "csr_ops.hpp"
+#include "gmres_kernels.hpp"
 
 namespace {
 
@@ -71,6 +72,12 @@ struct amgh_handle {
   real* scal = nullptr;      // device scalars: [0] norm/dot out, [1] rho, [2] rho_prev, [3] alpha, [4] beta, [5] tmp
   // internal fine-level buffers for host-pointer entry points and PCG
   real *x0 = nullptr, *b0 = nullptr, *pc_r = nullptr, *pc_c = nullptr, *pc_u = nullptr;
+  // GMRES (allocated by the first amgh_gmres): Krylov basis of gm_cols columns at leading dimension gm_ld, A v_k, the scalar
+  // block (gmres_kernels.hpp), kRedBlocks x kGmMaxRestart dot partials, flags; extra DGKS passes of the last call
+  real *gm_V = nullptr, *gm_t = nullptr, *gm_sc = nullptr, *gm_part = nullptr;
+  int* gm_flags = nullptr;
+  int64_t gm_ld = 0;
+  int gm_cols = 0, gm_reorth = -1;
   int64_t ws_bytes = 0;
   // profiling
   bool profile = false;
@@ -631,6 +638,116 @@ int pcg_dev(amgh_t* h, const real* b, real* x, int cyc, int use_precond, int max
   return bw_err_check();
 }
 
+// Restarted GMRES, IterativeSolvers.jl `gmres(A, b; Pl, restart, abstol, reltol, maxiter)` with x0 = 0 and left
+// preconditioning (Pl \ r = one cycle from x = 0, the reference's ldiv!, preconditioner.jl:12-19; use_precond = 0: Pl = I).
+//   (re)start: v1 = Pl \ (b - A x), beta = |v1|, v1 /= beta, residual estimate reset; tol = max(reltol beta0, abstol)
+//   step k:    w = Pl \ (A v_k), classical Gram-Schmidt with DGKS re-orthogonalisation (at most kGmMaxExtra extra passes),
+//              H[k+1, k] = |w|, v_{k+1} = w / |w|, null-vector update of the estimate `current`
+//   k == restart, or done (maxiter steps or current <= tol): least squares by Givens rotations, x += V y, restart unless done
+// The step's launches are fixed (gmres_kernels.hpp); the host reads `current` once per step (and beta once per restart).
+int gmres_blocks(int64_t n) {
+  return (int)std::max<int64_t>(1, std::min<int64_t>(kRedBlocks, (n / kGmVW + kThreads - 1) / kThreads));
+}
+
+int gmres_launch_dots(amgh_t* h, int k, const real* w, int64_t n, int nb, int pass) {
+  const real* V = h->gm_V;
+  const int64_t ld = h->gm_ld;
+  if (k <= 8) hipLaunchKernelGGL(gmres_dots_kernel<8>, dim3(nb), dim3(kThreads), 0, h->stream, V, ld, k, w, n, h->gm_part, (const int*)h->gm_flags, pass);
+  else if (k <= 16) hipLaunchKernelGGL(gmres_dots_kernel<16>, dim3(nb), dim3(kThreads), 0, h->stream, V, ld, k, w, n, h->gm_part, (const int*)h->gm_flags, pass);
+  else if (k <= 32) hipLaunchKernelGGL(gmres_dots_kernel<32>, dim3(nb), dim3(kThreads), 0, h->stream, V, ld, k, w, n, h->gm_part, (const int*)h->gm_flags, pass);
+  else hipLaunchKernelGGL(gmres_dots_kernel<64>, dim3(nb), dim3(kThreads), 0, h->stream, V, ld, k, w, n, h->gm_part, (const int*)h->gm_flags, pass);
+  HIP_TRY(hipGetLastError());
+  return AMGH_OK;
+}
+
+int gmres_launch_update(amgh_t* h, int k, real* w, int64_t n, int nb, int pass) {
+  const real* V = h->gm_V;
+  const int64_t ld = h->gm_ld;
+  const real* sc = h->gm_sc;
+  if (k <= 8) hipLaunchKernelGGL(gmres_update_kernel<8>, dim3(nb), dim3(kThreads), 0, h->stream, V, ld, k, w, n, sc, h->partial, (const int*)h->gm_flags, pass);
+  else if (k <= 16) hipLaunchKernelGGL(gmres_update_kernel<16>, dim3(nb), dim3(kThreads), 0, h->stream, V, ld, k, w, n, sc, h->partial, (const int*)h->gm_flags, pass);
+  else if (k <= 32) hipLaunchKernelGGL(gmres_update_kernel<32>, dim3(nb), dim3(kThreads), 0, h->stream, V, ld, k, w, n, sc, h->partial, (const int*)h->gm_flags, pass);
+  else hipLaunchKernelGGL(gmres_update_kernel<64>, dim3(nb), dim3(kThreads), 0, h->stream, V, ld, k, w, n, sc, h->partial, (const int*)h->gm_flags, pass);
+  HIP_TRY(hipGetLastError());
+  return AMGH_OK;
+}
+
+// v1 = Pl \ r with r = b (x = 0) or b - A x (restart); beta = |v1| (also to the host), v1 /= beta, the estimate reset
+int gmres_start(amgh_t* h, const real* b, const real* x, int cyc, int use_precond, bool restarted, real* beta) {
+  const int64_t n = fine_n(h);
+  real* v1 = h->gm_V;
+  const real* r = b;
+  if (restarted) { RC_TRY(fine_residual(h, x, b, h->gm_t)); r = h->gm_t; }
+  if (use_precond) {
+    RC_TRY(vec_fill(h, v1, n, 0.0));
+    RC_TRY(apply_cycle(h, v1, r, cyc, true));
+  } else {
+    RC_TRY(vec_copy(h, v1, r, n));
+  }
+  RC_TRY(vec_dot(h, v1, v1, n, h->gm_sc + kGmS + 1, 1));
+  hipLaunchKernelGGL(gmres_start_kernel, dim3(1), dim3(1), 0, h->stream, h->gm_sc);
+  hipLaunchKernelGGL(gmres_scale_kernel, dim3(grid_for(n)), dim3(256), 0, h->stream, v1, (const real*)(h->gm_sc + kGmS + 5), n);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(beta, h->gm_sc + kGmS + 1, sizeof(real), hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  return AMGH_OK;
+}
+
+int gmres_dev(amgh_t* h, const real* b, real* x, int cyc, int use_precond, int restart, int maxiter, double abstol,
+              double reltol, real* hist, int* iters) {
+  const int64_t n = fine_n(h);
+  const int nb = gmres_blocks(n);
+  auto col = [h](int j) { return h->gm_V + (int64_t)j * h->gm_ld; };
+  RC_TRY(vec_fill(h, x, n, 0.0));
+  HIP_TRY(hipMemsetAsync(h->gm_flags, 0, sizeof(int) * kGmFlags, h->stream));
+  real beta = 0.0;
+  RC_TRY(gmres_start(h, b, x, cyc, use_precond, false, &beta));
+  const real tol = std::max((double)reltol * beta, abstol);
+  if (hist) hist[0] = beta;
+  real current = beta;
+  int it = 0, k = 0;
+  while (it < maxiter && current > tol) {
+    real* w = col(k + 1);
+    if (use_precond) {
+      RC_TRY(fine_spmv(h, col(k), h->gm_t));
+      RC_TRY(vec_fill(h, w, n, 0.0));
+      RC_TRY(apply_cycle(h, w, h->gm_t, cyc, true));
+    } else {
+      RC_TRY(fine_spmv(h, col(k), w));
+    }
+    for (int pass = 0; pass <= kGmMaxExtra; ++pass) {
+      RC_TRY(gmres_launch_dots(h, k + 1, w, n, nb, pass));
+      hipLaunchKernelGGL(gmres_reduce_kernel, dim3(1), dim3(kThreads), 0, h->stream, (const real*)h->gm_part, nb, k + 1, k, h->gm_sc,
+                         (const int*)h->gm_flags, pass);
+      RC_TRY(gmres_launch_update(h, k + 1, w, n, nb, pass));
+      hipLaunchKernelGGL(gmres_norm_kernel, dim3(1), dim3(kThreads), 0, h->stream, (const real*)h->partial, nb, k, h->gm_sc, h->gm_flags, pass);
+    }
+    hipLaunchKernelGGL(gmres_scale_kernel, dim3(grid_for(n)), dim3(256), 0, h->stream, w, (const real*)(h->gm_sc + kGmS + 5), n);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(&current, h->gm_sc + kGmS, sizeof(real), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    ++it;
+    ++k;
+    if (hist) hist[it] = current;
+    const bool done = it >= maxiter || current <= tol;
+    if (k == restart || done) {
+      hipLaunchKernelGGL(gmres_lsq_kernel, dim3(1), dim3(kThreads), 0, h->stream, h->gm_sc, k);
+      hipLaunchKernelGGL(gmres_xupdate_kernel, dim3(grid_for(n)), dim3(256), 0, h->stream, (const real*)h->gm_V, h->gm_ld, k,
+                         (const real*)h->gm_sc, x, n);
+      HIP_TRY(hipGetLastError());
+      k = 0;
+      if (!done) RC_TRY(gmres_start(h, b, x, cyc, use_precond, true, &current));
+    }
+  }
+  if (iters) *iters = it;
+  int extra = 0;
+  HIP_TRY(hipMemcpyAsync(&extra, h->gm_flags + 1, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  h->gm_reorth = extra;
+  RC_TRY(prof_flush(h));
+  return bw_err_check();
+}
+
 int check_ready(const amgh_t* h) {
   if (!h) return AMGH_EINVAL;
   if (!h->finalized) return AMGH_ESTATE;
@@ -715,6 +832,7 @@ void amgh_destroy(amgh_t* h) {
   csr_free(&h->finalA);
   hipFree(h->coarse_op); hipFree(h->res_final); hipFree(h->partial); hipFree(h->scal);
   hipFree(h->x0); hipFree(h->b0); hipFree(h->pc_r); hipFree(h->pc_c); hipFree(h->pc_u);
+  hipFree(h->gm_V); hipFree(h->gm_t); hipFree(h->gm_sc); hipFree(h->gm_part); hipFree(h->gm_flags);
   for (auto& t : h->tail) hipFree(t.M);
   for (auto& e : h->pending) { hipEventDestroy(e.a); hipEventDestroy(e.b); }
   for (auto& g : h->graphs) if (g.exec) hipGraphExecDestroy(g.exec);
@@ -1475,6 +1593,57 @@ int amgh_pcg(amgh_t* h, const real* b, real* x, int cycle_, int use_precond, int
   HIP_TRY(hipMemcpy(x, h->x0, sizeof(real) * n, hipMemcpyDeviceToHost));
   return AMGH_OK;
 }
+
+static int ensure_gmres_bufs(amgh_t* h, int restart) {
+  const int64_t n = fine_n(h);
+  if (!h->gm_t) {
+    RC_TRY(dev_alloc(&h->gm_t, n));
+    RC_TRY(dev_alloc(&h->gm_sc, kGmReals));
+    RC_TRY(dev_alloc(&h->gm_part, (int64_t)kRedBlocks * kGmMaxRestart));
+    RC_TRY(dev_alloc(&h->gm_flags, kGmFlags));
+    HIP_TRY(hipMemsetAsync(h->gm_sc, 0, sizeof(real) * kGmReals, h->stream));
+    h->ws_bytes += kRealB * (n + kGmReals + (int64_t)kRedBlocks * kGmMaxRestart) + (int64_t)sizeof(int) * kGmFlags;
+  }
+  if (h->gm_V && h->gm_cols >= restart + 1) return AMGH_OK;
+  const int64_t per = 256 / kRealB;   // every column on a 256-byte boundary
+  const int64_t ld = (n + per - 1) / per * per;
+  if (h->gm_V) {
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    hipFree(h->gm_V);
+    h->gm_V = nullptr;
+    h->ws_bytes -= kRealB * h->gm_ld * h->gm_cols;
+    h->gm_cols = 0;
+  }
+  RC_TRY(dev_alloc(&h->gm_V, ld * (restart + 1)));
+  h->gm_ld = ld;
+  h->gm_cols = restart + 1;
+  h->ws_bytes += kRealB * ld * (restart + 1);
+  return AMGH_OK;
+}
+
+int amgh_gmres_d(amgh_t* h, const real* b_d, real* x_d, int cycle_, int use_precond, int restart, int maxiter, double abstol,
+                 double reltol, real* resid_hist, int* iters) {
+  RC_TRY(check_ready(h));
+  if (!b_d || !x_d || cycle_ < 0 || cycle_ > 2 || maxiter < 0 || restart < 1 || restart > kGmMaxRestart) return AMGH_EINVAL;
+  if (h->nrhs != 1) return AMGH_EUNSUPPORTED;  // IterativeSolvers' gmres takes vectors
+  HIP_TRY(hipSetDevice(h->device));
+  RC_TRY(ensure_gmres_bufs(h, restart));
+  return gmres_dev(h, b_d, x_d, cycle_, use_precond, restart, maxiter, abstol, reltol, resid_hist, iters);
+}
+
+int amgh_gmres(amgh_t* h, const real* b, real* x, int cycle_, int use_precond, int restart, int maxiter, double abstol,
+               double reltol, real* resid_hist, int* iters) {
+  RC_TRY(check_ready(h));
+  if (!b || !x) return AMGH_EINVAL;
+  HIP_TRY(hipSetDevice(h->device));
+  const int64_t n = fine_n(h);
+  HIP_TRY(hipMemcpyAsync(h->b0, b, sizeof(real) * n, hipMemcpyHostToDevice, h->stream));
+  RC_TRY(amgh_gmres_d(h, h->b0, h->x0, cycle_, use_precond, restart, maxiter, abstol, reltol, resid_hist, iters));
+  HIP_TRY(hipMemcpy(x, h->x0, sizeof(real) * n, hipMemcpyDeviceToHost));
+  return AMGH_OK;
+}
+
+int amgh_debug_gmres_reorth(const amgh_t* h) { return h ? h->gm_reorth : -1; }
 
 static amgh_csr* level_op(amgh_t* h, int level, int which) {
   const int L = (int)h->levels.size();

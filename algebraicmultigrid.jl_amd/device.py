@@ -338,6 +338,25 @@ class DeviceHierarchy:
                                     abstol, reltol, hist.ctypes.data, C.byref(iters)), "pcg")
         return x, hist[:iters.value + 1].copy(), iters.value
 
+    def gmres(self, b, cycle=CYCLE_V, use_precond=True, restart=None, maxiter=None, abstol=0.0, reltol=None):
+        """Restarted, left-preconditioned GMRES on the device (amgh_gmres): IterativeSolvers.jl's gmres with x0 = 0.
+        restart defaults to min(20, n), maxiter (Arnoldi steps) to n, reltol to sqrt(eps).  Returns (x, hist, iters):
+        hist[0] = |Pl \\ b|, then the residual estimate after each step."""
+        b = np.ascontiguousarray(b, dtype=self.dtype)
+        restart = min(20, self.n) if restart is None else int(restart)
+        maxiter = self.n if maxiter is None else int(maxiter)
+        reltol = float(np.sqrt(np.finfo(self.dtype).eps)) if reltol is None else float(reltol)
+        x = np.zeros_like(b)
+        hist = np.zeros(max(maxiter, 0) + 1, dtype=self.dtype)
+        iters = C.c_int(0)
+        hip_check(self.lib.amgh_gmres(self.h, b.ctypes.data, x.ctypes.data, cycle, int(bool(use_precond)), restart, maxiter,
+                                      float(abstol), reltol, hist.ctypes.data, C.byref(iters)), "gmres")
+        return x, hist[:iters.value + 1].copy(), iters.value
+
+    def gmres_reorth_passes(self):
+        """DGKS re-orthogonalisation passes of the last gmres call (-1: none yet)."""
+        return int(self.lib.amgh_debug_gmres_reorth(self.h))
+
     # ---- per-level hooks -----------------------------------------------------
     def spmv(self, level, which, x):
         x = np.ascontiguousarray(x, dtype=self.dtype)

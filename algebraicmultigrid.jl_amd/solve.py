@@ -239,3 +239,37 @@ def cg(A, b, Pl=None, abstol=0.0, reltol=_SQRT_EPS, maxiter=None, log=False):
     if log:
         return x, {"iters": iters, "resnorm": hist[1:], "isconverged": bool(hist[-1] <= max(reltol * hist[0], abstol))}
     return x
+
+
+def gmres(A, b, Pl=None, restart=None, abstol=0.0, reltol=None, maxiter=None, log=False):
+    """IterativeSolvers.jl `gmres(A, b; Pl, restart, abstol, reltol, maxiter, log)` with x0 = 0: restarted GMRES for
+    nonsymmetric operators, left-preconditioned by one cycle of Pl's hierarchy (`ldiv!`, preconditioner.jl:12-19) — the
+    pairing the reference's preconditioner builders (precs.jl) exist for.  Runs entirely on device (amgh_gmres); A must be
+    the fine-level operator of Pl's hierarchy.
+
+    (Re)start: v1 = Pl \\ (b - A x), beta = |v1|.  Each Arnoldi step w = Pl \\ (A v_k) is orthogonalised by classical
+    Gram-Schmidt with the DGKS test (another pass while |w| < |h| / sqrt(2), at most 2 extra passes), and the residual
+    estimate `current` comes from IterativeSolvers' null-vector update.  After `restart` steps, or when done (maxiter
+    steps or current <= max(reltol * beta0, abstol)), H y ~ beta e1 is solved by Givens rotations and x += V y.
+    restart defaults to min(20, n) (1..64), maxiter (Arnoldi steps) to n, reltol to sqrt(eps(T)).  The residual is the
+    PRECONDITIONED one, |Pl \\ (b - A x)|.  With log: (x, {"iters", "resnorm", "isconverged"})."""
+    if not isinstance(Pl, Preconditioner):
+        raise AMGError("gmres: Pl must be aspreconditioner(ml)")
+    ml = Pl.ml
+    A = SparseMatrixCSC.coerce(A)
+    fine = ml.levels[0].A if ml.levels else ml.final_A
+    if A is not fine and not (A.shape == fine.shape and A.nnz == fine.nnz and np.array_equal(A.colptr, fine.colptr)
+                              and np.array_equal(A.rowval, fine.rowval) and np.array_equal(A.nzval, fine.nzval)):
+        raise AMGError("gmres: A must be the operator the preconditioner was built from")
+    dt = _arith_dtype(ml, b)
+    reltol = float(np.sqrt(np.finfo(dt).eps)) if reltol is None else float(reltol)
+    b = np.asarray(b, dtype=dt)
+    if b.ndim != 1:
+        raise AMGError("gmres: b must be a vector")
+    maxiter = A.n if maxiter is None else int(maxiter)
+    restart = min(20, A.n) if restart is None else int(restart)
+    x, hist, iters = ml.device(dtype=dt).gmres(b, _cycle_code(Pl.cycle), True, restart, maxiter, float(abstol), reltol)
+    if log:
+        tol = max(reltol * float(hist[0]), float(abstol))
+        return x, {"iters": iters, "resnorm": hist[1:], "isconverged": bool(hist[-1] <= tol)}
+    return x

@@ -243,6 +243,19 @@ int amgh_pcg(amgh_t* h, const amgh_real* b, amgh_real* x, int cycle, int use_pre
 int amgh_pcg_d(amgh_t* h, const amgh_real* b_d, amgh_real* x_d, int cycle, int use_precond,
                int maxiter, double abstol, double reltol, amgh_real* resid_hist, int* iters);
 
+/* gmres(A, b; Pl = aspreconditioner(ml), restart, abstol, reltol, maxiter) — IterativeSolvers.jl's restarted GMRES for
+ * nonsymmetric operators, the Krylov method the reference's preconditioner builders (precs.jl) hand AMG to, entirely on
+ * device; x0 = 0.  Left preconditioning: Pl \ r is one cycle from x = 0 (ldiv!, preconditioner.jl:12-19);
+ * use_precond = 0 gives Pl = I.  Classical Gram-Schmidt with DGKS re-orthogonalisation, at most 2 extra passes per step.
+ * restart in [1, 64]; maxiter counts Arnoldi steps; stop when the residual estimate <= max(reltol*|Pl\b|, abstol).
+ * resid_hist: NULL or maxiter+1 reals ([0] = |Pl \ b|, then the estimate after each step).  nrhs == 1 only.       */
+int amgh_gmres(amgh_t* h, const amgh_real* b, amgh_real* x, int cycle, int use_precond, int restart,
+               int maxiter, double abstol, double reltol, amgh_real* resid_hist, int* iters);
+int amgh_gmres_d(amgh_t* h, const amgh_real* b_d, amgh_real* x_d, int cycle, int use_precond, int restart,
+                 int maxiter, double abstol, double reltol, amgh_real* resid_hist, int* iters);
+/* Diagnostics: DGKS re-orthogonalisation passes the handle's last amgh_gmres(_d) call ran (-1: none yet). */
+int amgh_debug_gmres_reorth(const amgh_t* h);
+
 /* ------------------------------------------------------------------------- */
 /* Per-level operators — unit-test and roofline hooks                           */
 /* ------------------------------------------------------------------------- */
