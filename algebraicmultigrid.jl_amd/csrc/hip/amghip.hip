@@ -44,7 +44,6 @@ struct Level {
   // of b / scatter of x on the next level, and the gathers of R and P stay local (a coarse hyperplane's fine
   // neighbours sit in adjacent fine hyperplanes)
   bool coarse_lo = false;
-  bool nat_freed = false;  // memory-lean: the natural-order A (levels >= 1), P and R were released, the cycle runs level-ordered
 };
 
 }  // namespace
@@ -279,7 +278,7 @@ int cycle(amgh_t* h, int l, real* x, const real* b, int cyc, bool xzero, bool lo
   // and residual / restriction / prolongation run on level-ordered copies of A, R, P (same entries in the same
   // order inside every row, so the same sums): no scatter after the pre-smoother, no gather before the post-smoother.
   GsSchedule* g = L->smat()->gs;
-  const bool lo = L->lo_ok && (g_gs_keep_lo || L->nat_freed || lo_io) && g && g->nblk == 0;
+  const bool lo = L->lo_ok && g && g->nblk == 0;
   if (lo_io && !lo) return AMGH_ESTATE;   // (cannot happen: the level above only hands over in level order what was built for it)
   {
     ProfScope p(h, AMGH_T_PRESMOOTH, l);
@@ -963,7 +962,7 @@ static int level_prepare(int device, int64_t n, const int32_t* A_rowptr, const i
     // coarse operator): the level-ordered cycle needs A's VALUES on the schedule's copy of S — possible when the two
     // have the same pattern (then row perm[p] of A lists the same columns in the same order as row p of the copy)
     bool same_pattern = !L->has_S;
-    if (L->has_S && rc == AMGH_OK && both && g->nblk == 0 && g_gs_keep_lo && (int64_t)g->h_perm.size() == n &&
+    if (L->has_S && rc == AMGH_OK && both && g->nblk == 0 && (int64_t)g->h_perm.size() == n &&
         A_rowptr[n] == S_rowptr[n] && std::equal(A_rowptr, A_rowptr + n + 1, S_rowptr) &&
         std::equal(A_col, A_col + A_rowptr[n], S_col)) {
       const std::vector<int32_t>& perm = g->h_perm;
@@ -982,7 +981,7 @@ static int level_prepare(int device, int64_t n, const int32_t* A_rowptr, const i
       if (same_pattern) M->bytes += kRealB * (int64_t)lv.size();
     }
     // what the second half needs to know: the level-ordered P / R are wanted (g->h_perm is kept until then)
-    L->lo_want = rc == AMGH_OK && both && same_pattern && g->nblk == 0 && g_gs_keep_lo && (int64_t)g->h_perm.size() == n;
+    L->lo_want = rc == AMGH_OK && both && same_pattern && g->nblk == 0 && (int64_t)g->h_perm.size() == n;
     if (g && !L->lo_want) std::vector<int32_t>().swap(g->h_perm);
   }
   if (rc != AMGH_OK) {
@@ -1102,7 +1101,6 @@ int amgh_push_level_end(amgh_t* h, int64_t nc, const int32_t* P_rowptr, const in
     };
     drop(&L->P); drop(&L->R);
     if (!h->levels.empty()) { drop(&L->A); if (L->has_S) drop(&L->S); }
-    L->nat_freed = true;
   }
   h->pending_level = nullptr;
   if (rc != AMGH_OK) {
@@ -1119,7 +1117,7 @@ int amgh_push_level_end(amgh_t* h, int64_t nc, const int32_t* P_rowptr, const in
   }
   // this level runs the level-ordered cycle: the level above hands its coarse vectors over in that order (the last step:
   // it either renumbers the previous level's coarse side completely or leaves it untouched, and nothing after it can fail)
-  if (L->lo_ok && g && g->nblk == 0 && g_gs_keep_lo && g_gs_coarse_lo && !h->levels.empty() && h->levels.back()->lo_ok && h->nrhs >= 1) {
+  if (L->lo_ok && g && g->nblk == 0 && g_gs_coarse_lo && !h->levels.empty() && h->levels.back()->lo_ok && h->nrhs >= 1) {
     rc = coarse_side_to_level_order(h->levels.back(), g);
     if (rc != AMGH_OK) { level_discard(L); return rc; }
   }
@@ -1202,9 +1200,9 @@ int amgh_finalize(amgh_t* h) {
     for (size_t l = 0; l < h->levels.size(); ++l)
       if (h->levels[l]->n <= g_tail_dense_rows) { h->tail_level = (int)l; break; }
   if (h->tail_level >= 0) {
-    int bb = std::max(1, std::min(g_tail_dense_batch, 64));
-    if (bb == 2 || bb == 4 || bb == 8 || bb == 16) bb += 1;   // (not a block size of the interleaved kernels: their buffers belong to the handle's own block)
-    h->tail_cols = bb;
+    // 64 columns of the identity at a time (the largest block of right-hand sides: 256^3 174 -> ~140 ms, C1 17.8 -> 12.0 ms
+    // against 32; profiles/r06_tail_dense.log)
+    h->tail_cols = 64;
     h->tail_lo = h->tail_level >= 1 && h->levels[h->tail_level - 1]->coarse_lo;
   }
   for (size_t l = 0; l < h->levels.size(); ++l) {
@@ -1274,7 +1272,7 @@ int amgh_finalize(amgh_t* h) {
   }
   // The restriction of a big level with the XCD-contiguous mapping of its workgroups where that is faster (a coarse row gathers from a
   // fine vector several times its own size: which L2 holds the lines matters) — timed here on the level's own buffers, single column.
-  if (h->nrhs == 1 && g_stream_xcd)
+  if (h->nrhs == 1)
     for (Level* L : h->levels) {
       if (!L->lo_ok || !L->Rp.rowptr || L->Rp.nrows < (1 << 18)) continue;
       if (hipMemsetAsync(L->res, 0, sizeof(real) * L->n, h->stream) != hipSuccess) return -1001;
@@ -2264,28 +2262,16 @@ int amgh_debug_merged_sweep_host(int64_t nrows, int64_t ncols, const int32_t* ro
 
 int amgh_debug_set_tunable(const char* name, int value) {
   if (!name) return AMGH_EINVAL;
-  if (!strcmp(name, "gs_block_target")) g_gs_block_target = value;
-  else if (!strcmp(name, "gs_min_rows")) g_gs_min_rows = value;
-  else if (!strcmp(name, "gs_nnz_per_wg")) g_gs_nnz_per_wg = value;
-  else if (!strcmp(name, "gs_threads")) g_gs_threads = value;
-  else if (!strcmp(name, "gs_block_inverse")) g_gs_block_inverse = value;
-  else if (!strcmp(name, "gs_slots")) g_gs_slots = value;
-  else if (!strcmp(name, "gs_xcd_map")) g_gs_xcd_map = value;
+  if (!strcmp(name, "gs_block_inverse")) g_gs_block_inverse = value;
   else if (!strcmp(name, "gs_lpr")) g_gs_lpr = value;
   else if (!strcmp(name, "gs_il")) g_gs_il = value;
   else if (!strcmp(name, "trim_coded")) g_trim_coded = value;
   else if (!strcmp(name, "gs_wave_quad")) g_gs_wave_quad = value;
   else if (!strcmp(name, "pcg_fused")) g_pcg_fused = value;
-  else if (!strcmp(name, "gs_tri_rb")) g_gs_tri_rb = value;
-  else if (!strcmp(name, "gs_tri_rb1")) g_gs_tri_rb1 = value;
-  else if (!strcmp(name, "gs_dti_pre")) g_gs_dti_pre = value;
-  else if (!strcmp(name, "stream_xcd")) g_stream_xcd = value;
   else if (!strcmp(name, "tail_dense_rows")) g_tail_dense_rows = value < 0 ? 0 : value;
   else if (!strcmp(name, "tail_dense")) { g_tail_dense = value; g_sched_epoch++; }   // (captured cycles hold the path they were captured on)
-  else if (!strcmp(name, "tail_dense_batch")) g_tail_dense_batch = value;
   else if (!strcmp(name, "gs_lean")) g_gs_lean = value;
   else if (!strcmp(name, "gs_sell")) g_gs_sell = value;
-  else if (!strcmp(name, "gs_sample")) g_gs_sample = value;
   else if (!strcmp(name, "gs_tiny")) g_gs_tiny = value;
   else if (!strcmp(name, "gs_bw")) g_gs_bw = value;
   else if (!strcmp(name, "gs_bw_rows")) g_gs_bw_rows = value;
@@ -2295,12 +2281,8 @@ int amgh_debug_set_tunable(const char* name, int value) {
   else if (!strcmp(name, "gs_bw_nc")) g_gs_bw_nc = value;
   else if (!strcmp(name, "gs_bw_nrhs")) g_gs_bw_nrhs = value;
   else if (!strcmp(name, "gs_bw_skip_pub")) g_gs_bw_skip_pub = value;
-  else if (!strcmp(name, "gs_bw_min_rows")) g_gs_bw_min_rows = value;
   else if (!strcmp(name, "gs_bw_two_min_rows")) g_gs_bw_two_min_rows = value;
-  else if (!strcmp(name, "gs_dup_launch")) g_gs_dup_launch = value < 0 ? 0 : value > 16 ? 16 : value;   // (a repeat count: never negative)
   else if (!strcmp(name, "gs_flow_xzero")) g_gs_flow_xzero = value;
-  else if (!strcmp(name, "gs_bw_grid")) g_gs_bw_grid = value < 0 ? 0 : value;
-  else if (!strcmp(name, "gs_bw_grid_long")) g_gs_bw_grid_long = value < 0 ? 0 : value;
   else if (!strcmp(name, "gs_bw_dict")) g_gs_bw_dict = value != 0;
   else if (!strcmp(name, "gs_bw_inorder")) g_gs_bw_inorder = value != 0;
   else if (!strcmp(name, "stream_code")) g_stream_code = value != 0;
@@ -2309,17 +2291,10 @@ int amgh_debug_set_tunable(const char* name, int value) {
   else if (!strcmp(name, "jacobi_zero")) g_jacobi_zero = value;
   else if (!strcmp(name, "gs_ept")) g_gs_ept = value;
   else if (!strcmp(name, "gs_merge")) g_gs_merge = value;
-  else if (!strcmp(name, "gs_merge_force")) g_gs_merge_force = value;
-  else if (!strcmp(name, "gs_merge_force_maxn")) g_gs_merge_force_maxn = value;
-  else if (!strcmp(name, "gs_zone")) g_gs_zone = value;
   else if (!strcmp(name, "gs_coarse_lo")) g_gs_coarse_lo = value;
   else if (!strcmp(name, "gs_dense_tri")) g_gs_dense_tri = value;
   else if (!strcmp(name, "gs_dense_blk")) g_gs_dense_blk = value;
-  else if (!strcmp(name, "gs_zone_t0_ns")) g_gs_zone_t0_ns = value;
-  else if (!strcmp(name, "gs_zone_floor_ns")) g_gs_zone_floor_ns = value;
   else if (!strcmp(name, "gs_bigslot")) g_gs_bigslot = value;
-  else if (!strcmp(name, "gs_flip")) g_gs_flip = value;
-  else if (!strcmp(name, "gs_keep_lo")) g_gs_keep_lo = value;
   else if (!strcmp(name, "gs_super")) g_gs_super = value;
   else if (!strcmp(name, "gs_block_pipe")) g_gs_block_pipe = value;
   else return AMGH_EINVAL;

@@ -391,25 +391,12 @@ struct amgh_csr {
 
 namespace {
 
-// launch-shape tunables of the per-level Gauss-Seidel launches (amgh_debug_set_tunable)
-int g_gs_block_target = 256;   // aim for at least this many workgroups per wide level
-int g_gs_min_rows = 4;         // but never fewer rows per workgroup than this
-int g_gs_nnz_per_wg = 256;     // and about this many nonzeros per workgroup (one per thread)
-int g_gs_threads = 256;
+// tunables of the smoothers and the cycle (amgh_debug_set_tunable)
 int g_gs_block_pipe = 1;        // software-pipelined block sweep (gs_block_pipe_kernel)
 int g_gs_super = 8;             // block-inverse sweeps: blocks per superblock (0 = one launch for the whole operator); read at schedule build
-int g_gs_coarse_lo = 1;         // ... and hand the coarse vectors of a level over in the next level's order (read at amgh_push_level)
-int g_gs_keep_lo = 1;           // keep x in level order between pre- and post-smoother (level-ordered residual, R, P)
-int g_gs_flip = 1;              // alternating merged sweeps: s of the next sweep from the last one (no matrix pass)
+int g_gs_coarse_lo = 1;         // level-ordered cycle: hand the coarse vectors of a level over in the next level's order (read at amgh_push_level)
 int g_gs_bigslot = 1;           // allow long-row slots (composite rows up to 2048 entries) when merging
 int g_gs_merge = 16;             // merged-level sweeps: largest group of dependency levels tried (1 = off); read at schedule build
-int g_gs_zone_t0_ns = 3000;      // ... its per-launch price (ns) and the floor below which a launch does not get cheaper (ns; 0 = none)
-int g_gs_zone_floor_ns = 0;
-int g_gs_zone = 1;               // groups of different depth along a sweep (deep where levels are small); read at schedule build
-int g_gs_merge_force_maxn = 0;   // ... only on operators with at most this many rows (0 = all)
-int g_gs_merge_force = 0;        // measurement hook: groups of exactly this many levels wherever they can be built (0 = cost model); read at schedule build
-int g_gs_xcd_map = 1;           // XCD-contiguous slot -> workgroup mapping in gs_slot_kernel
-int g_gs_slots = 1;             // wide levels from the slot layout (0 = CSR stream kernel)
 int g_jacobi_zero = 1;          // Jacobi on x = 0 as a vector kernel (0 = the full sweep); read at every sweep
 int g_rhs_il = 1;               // blocks of 2 / 4 / 8 / 16 right-hand sides: restriction and prolongation gather an interleaved copy of their input (0 = column by column); read at every cycle
 int g_gs_tiny = 1;              // an operator that fits LDS entirely: 1 = gs_wave_kernel where its record was built, else gs_chain_tiny_kernel; 2 = gs_chain_tiny_kernel; 0 = gs_chain_kernel; read at every sweep
@@ -427,13 +414,8 @@ int g_trim_coded = 1;           // trimmed / lean footprint: operators of the le
 int g_gs_bw_inorder = 0;        // 1: the relayed single-column sweep sums every row in stored entry order (the scalar loop's bits); 0 (default): where the records allow it (GsSchedule::Bw::FlowDev::late_ok) the products with the sweep's FAR side — x values that cannot change any more — are summed above the hand-over and the near half is added below it: the same Gauss-Seidel iterate, one reassociation per row (<= 1 ulp-level differences), a shorter dependent tail per step; read at every sweep
 int g_gs_bw_dict = 1;           // the relayed single-column sweep reads the dictionary layout where a schedule carries one (bw::FlowDict: half the bytes of a 7-point level's sweep; bitwise the same); read at schedule build (0: not built) and at every sweep
 int g_gs_bw_relay = 3;          // walker waves a single-column dataflow sweep relays a block's walk between (gs_relay.hpp: the one instantiated count, BW_RELAY_W; 0: one walker, gs_bw_flow_kernel — bitwise the same); read at every sweep
-int g_gs_bw_grid = 0;           // workgroups of a relayed single-column sweep (fewer than blocks: the persistent form of gs_relay.hpp; 0: one per block); read at every sweep
-int g_gs_bw_grid_long = 512;      // ... of levels with rows of more than 6 entries ON PLAIN RECORDS (critical-path bound: fewer resident blocks, faster hand-offs; the dictionary layout launches a workgroup per block); read at every sweep
 int g_gs_flow_xzero = 1;        // a dataflow sweep that starts a smooth! call on x = 0 reads no x (0: fill + read as any other sweep — bitwise the same); read at every sweep
-int g_gs_dup_launch = 0;        // measurement hook: every merged-group / level launch of a sweep issued 1 + this many times (idempotent); read at every sweep
-int g_gs_bw_two_min_rows = 200000;  // ... operators with TWO offset classes (2-D grids) take the wavefront of blocks from this many rows where the cost model agrees (0 = never); round 4: 6 000 000; with the relayed dataflow sweep 512^2 / 1024^2 / 2048^2 Poisson V-cycles 4.82 -> 3.92 / 9.35 -> 8.50 / 21.6 -> 18.3 ms, 4096^2 39.1 -> 39.9 (profiles/r05_block_layout_threshold.log); read at schedule build
-int g_gs_bw_min_rows = 30000;   // ... operators below this many rows keep the level schedules in mode 1 (half as many for rows of at most 7 entries).  Round 3 (chained kernel): 3 000 000; with the relayed dataflow sweep and its own cost model (Plan::est_flow_seconds) the block layout wins wherever that model says so: 48^3 ... 160^3 Poisson hierarchies -19 ... -28 % per V-cycle with the second level on it too (tools/minrows_sweep.py, profiles/r05_block_layout_threshold.log)
-int g_gs_sample = 1;            // candidate group sizes of the merged sweeps from a sample of the groups (0 = every candidate built in full); read at schedule build
+int g_gs_bw_two_min_rows = 200000;  // wavefront of blocks: operators with TWO offset classes (2-D grids) take it from this many rows where the cost model agrees (0 = never); round 4: 6 000 000; with the relayed dataflow sweep 512^2 / 1024^2 / 2048^2 Poisson V-cycles 4.82 -> 3.92 / 9.35 -> 8.50 / 21.6 -> 18.3 ms, 4096^2 39.1 -> 39.9 (profiles/r05_block_layout_threshold.log); read at schedule build
 int g_gs_sell = 1;              // merged groups from the SELL-like layout where it was built (0 = slot kernels); build: read at schedule build too
 int g_gs_lean = -1;             // footprint policy: -1 = AMGH_LEAN environment variable (unset: trim), 0 = full (every copy kept), 1 = lean, 2 = trim; read at schedule build
 int g_gs_ept = 0;               // entries per thread of merged slot launches (0 = 2 when a group has more than 1024 slots, else 1)
@@ -442,14 +424,9 @@ int g_gs_il = 1;                // blocks of 2 / 4 / 8 right-hand sides: merged 
 int g_pcg_fused = 1;            // amgh_pcg: 1 = the recurrence between two cycles in 8 launches (second stages of the dot products fused with the scalar steps, the updates with the norm); 0 = one launch per operation (15) — bitwise the same iterates
 int g_tail_dense_rows = 6144;   // the collapsed coarse tail: the first level with at most this many rows and everything below it become ONE dense operator (0 = off); read at amgh_finalize
 int g_tail_dense = 1;           // ... and is applied where it has been built (0 = the per-level cycle: what the operator was built from); read at every cycle
-int g_tail_dense_batch = 64;    // ... built from the library's own cycle on this many columns of the identity at a time (64 = the largest block of right-hand sides: 256^3 174 -> ~140 ms, C1 17.8 -> 12.0 ms against 32; profiles/r06_tail_dense.log); read at amgh_finalize
-int g_stream_xcd = 1;           // big SpMV-type operators whose timing at amgh_finalize asked for it run with the XCD-contiguous workgroup mapping (0 = never); read at amgh_finalize and at every launch
-int g_gs_dti_pre = 8;           // pre-pass of a dense-triangle block: rows per workgroup (8; 16 = the shape of rounds 2-5, bitwise the same); read at every sweep
-int g_gs_tri_rb1 = 0;           // ... and under a SINGLE column: rows per workgroup of the dense triangle inverses (0 = one row, tri_gemv_kernel; 2 / 4 / 8: tri_gemm_kernel<1, RB> — bitwise the same); read at every sweep
-int g_gs_tri_rb = 1;            // dense triangle inverses under a block of right-hand sides: 4 rows per workgroup (tri_gemm_kernel; 0 = one row, tri_gemv_kernel — bitwise the same); read at every sweep
-int g_gs_dense_blk = 4096;       // ... rows per dense block above kDenseTriMax rows; read at schedule build
+int g_gs_dense_blk = 4096;       // dense-triangle sweeps: rows per dense block above kDenseTriMax rows; read at schedule build
 int g_gs_dense_tri = 1;          // small operators: sweeps through the dense inverse of the whole triangle (0 = block-inverse / exact order); build + sweep
-int g_gs_block_inverse = 1;     // block-inverse sweeps for small densely coupled operators (0 = exact order everywhere)        // workgroup size of the per-level launches (64 or 256)
+int g_gs_block_inverse = 1;     // block-inverse sweeps for small densely coupled operators (0 = exact order everywhere)
 
 // bumped whenever a schedule buffer that captured hipGraphs may point to is reallocated or freed (xp / bp growth,
 // SOR child eviction): handles drop their cached graph execs when it has moved on

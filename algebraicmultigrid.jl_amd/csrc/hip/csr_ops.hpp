@@ -23,6 +23,9 @@ int launch_stream(const StreamArgs& a0, hipStream_t st, int ncolv = 1) {
 // One dependency level of a Gauss-Seidel / SOR sweep: a latency-bound launch, so the
 // rows are spread over many small workgroups (rows per workgroup chosen at schedule
 // build time from the level's average row length).
+constexpr int kGsBlockTarget = 256;   // aim for at least this many workgroups per wide level
+constexpr int kGsMinRows = 4;         // but never fewer rows per workgroup than this
+constexpr int kGsNnzPerWg = 256;      // and about this many nonzeros per workgroup (one per thread)
 template <int MODE>
 int launch_gs_level(const StreamArgs& a, int rows, hipStream_t st, int ncolv = 1) {
   // latency-bound launch: prefer many small workgroups over few full ones — a CU's
@@ -32,17 +35,8 @@ int launch_gs_level(const StreamArgs& a, int rows, hipStream_t st, int ncolv = 1
   const int width = a.row_end - a.row_begin;
   const int avg16 = std::max(16, rows);
   rows = 256;
-  while (rows > g_gs_min_rows && (int64_t)rows * avg16 > (int64_t)g_gs_nnz_per_wg * 16) rows >>= 1;
-  while (rows > g_gs_min_rows && width / rows < g_gs_block_target && (int64_t)rows * avg16 > 16 * 64) rows >>= 1;
-  if (g_gs_threads == 64) {
-    switch (rows) {
-      case 8: return launch_stream<MODE, StreamCfg<64, 8, 2048, 1, false, false>>(a, st, ncolv);
-      case 16: return launch_stream<MODE, StreamCfg<64, 16, 2048, 1, false, false>>(a, st, ncolv);
-      case 32: return launch_stream<MODE, StreamCfg<64, 32, 2048, 1, false, false>>(a, st, ncolv);
-      case 64: return launch_stream<MODE, StreamCfg<64, 64, 2048, 1, false, false>>(a, st, ncolv);
-      default: break;
-    }
-  }
+  while (rows > kGsMinRows && (int64_t)rows * avg16 > (int64_t)kGsNnzPerWg * 16) rows >>= 1;
+  while (rows > kGsMinRows && width / rows < kGsBlockTarget && (int64_t)rows * avg16 > 16 * 64) rows >>= 1;
   switch (rows) {
     case 4: return launch_stream<MODE, StreamCfg<256, 4, 2048, 1, false, false>>(a, st, ncolv);
     case 8: return launch_stream<MODE, StreamCfg<256, 8, 2048, 1, false, false>>(a, st, ncolv);
@@ -71,7 +65,7 @@ template <int MODE>
 int launch_stream_sized(const StreamArgs& a, hipStream_t st, int ncolv, bool xcd = false) {
   if (a.row_end - a.row_begin < (1 << 18)) return launch_stream<MODE, SmallCfg>(a, st, ncolv);
   if constexpr (MODE == M_SPMV) {
-    if (xcd && g_stream_xcd && ncolv == 1) {
+    if (xcd && ncolv == 1) {
       if (a.ccol && (g_stream_code || !a.col)) return launch_stream<MODE, StreamCfg<1024, 1024, 8192, 4, false, true>, true>(a, st, ncolv);
       return launch_stream<MODE, StreamCfg<1024, 1024, 8192, 4, false, true>>(a, st, ncolv);
     }
@@ -573,25 +567,17 @@ int csr_gs_sweep(amgh_csr* op, bool backward, bool sor, real omega, real* x, con
       ra.ldx = g->n; ra.ldy = g->n; ra.ldb = g->n;
       // (a block's rows are few and long: few per workgroup, or the pre-pass of a 4 096-row block runs on 64 CUs)
       // (8 rows per workgroup since round 6: 512 workgroups for a 4 096-row block — 14.135 -> 14.10 ms per 256^3 V-cycle against 16 rows,
-      // bitwise; 32 rows 14.25, 128 threads with 8 / 4 rows 14.15 / 14.11: profiles/r06_dense_tri_rows.log; tunable gs_dti_pre = 16: the old shape)
-      if (nb > 1 && g_gs_dti_pre != 16) RC_TRY((launch_stream<M_RESID, StreamCfg<256, 8, 4096, 2, false, false>>(ra, st, ncolv)));
-      else if (nb > 1) RC_TRY((launch_stream<M_RESID, StreamCfg<256, 16, 4096, 2, false, false>>(ra, st, ncolv)));
+      // bitwise; 32 rows 14.25, 128 threads with 8 / 4 rows 14.15 / 14.11: profiles/r06_dense_tri_rows.log)
+      if (nb > 1) RC_TRY((launch_stream<M_RESID, StreamCfg<256, 8, 4096, 2, false, false>>(ra, st, ncolv)));
       else RC_TRY((launch_stream<M_RESID, StreamCfg<256, 64, 4096, 2, false, false>>(ra, st, ncolv)));
       const real* Xk = (const real*)((backward ? g->dti_b : g->dti_f) + g->dti_off[k]);
       // columns per workgroup: the largest of 8 / 4 / 2 / 1 that divides the block of right-hand sides
-      // (blocks of right-hand sides: 4 rows per workgroup share the loads of s — tri_gemm_kernel, bitwise tri_gemv_kernel; tunable gs_tri_rb)
+      // (blocks of right-hand sides: 4 rows per workgroup share the loads of s — tri_gemm_kernel, bitwise tri_gemv_kernel)
       constexpr int RB = 4;
       const unsigned rgrid = (unsigned)((rb + RB - 1) / RB);
-      if (ncolv % 8 == 0 && g_gs_tri_rb) hipLaunchKernelGGL((tri_gemm_kernel<8, RB>), dim3(rgrid, ncolv / 8), dim3(kThreads), 0, st, Xk, (const real*)(g->blk_s + r0), x + r0, rb, backward ? 1 : 0, (int64_t)g->n, (int64_t)g->n);
-      else if (ncolv % 4 == 0 && g_gs_tri_rb) hipLaunchKernelGGL((tri_gemm_kernel<4, RB>), dim3(rgrid, ncolv / 4), dim3(kThreads), 0, st, Xk, (const real*)(g->blk_s + r0), x + r0, rb, backward ? 1 : 0, (int64_t)g->n, (int64_t)g->n);
-      else if (ncolv % 2 == 0 && g_gs_tri_rb) hipLaunchKernelGGL((tri_gemm_kernel<2, RB>), dim3(rgrid, ncolv / 2), dim3(kThreads), 0, st, Xk, (const real*)(g->blk_s + r0), x + r0, rb, backward ? 1 : 0, (int64_t)g->n, (int64_t)g->n);
-      else if (ncolv % 8 == 0) hipLaunchKernelGGL(tri_gemv_kernel<8>, dim3((unsigned)rb, ncolv / 8), dim3(kThreads), 0, st, Xk, (const real*)(g->blk_s + r0), x + r0, rb, backward ? 1 : 0, (int64_t)g->n, (int64_t)g->n);
-      else if (ncolv % 4 == 0) hipLaunchKernelGGL(tri_gemv_kernel<4>, dim3((unsigned)rb, ncolv / 4), dim3(kThreads), 0, st, Xk, (const real*)(g->blk_s + r0), x + r0, rb, backward ? 1 : 0, (int64_t)g->n, (int64_t)g->n);
-      else if (ncolv % 2 == 0) hipLaunchKernelGGL(tri_gemv_kernel<2>, dim3((unsigned)rb, ncolv / 2), dim3(kThreads), 0, st, Xk, (const real*)(g->blk_s + r0), x + r0, rb, backward ? 1 : 0, (int64_t)g->n, (int64_t)g->n);
-      // (single columns: several rows per workgroup share the loads of s too — tunable gs_tri_rb1 = 2 / 4 / 8 rows, bitwise the one-row kernel)
-      else if (g_gs_tri_rb1 == 2) hipLaunchKernelGGL((tri_gemm_kernel<1, 2>), dim3((unsigned)((rb + 1) / 2), ncolv), dim3(kThreads), 0, st, Xk, (const real*)(g->blk_s + r0), x + r0, rb, backward ? 1 : 0, (int64_t)g->n, (int64_t)g->n);
-      else if (g_gs_tri_rb1 == 4) hipLaunchKernelGGL((tri_gemm_kernel<1, 4>), dim3((unsigned)((rb + 3) / 4), ncolv), dim3(kThreads), 0, st, Xk, (const real*)(g->blk_s + r0), x + r0, rb, backward ? 1 : 0, (int64_t)g->n, (int64_t)g->n);
-      else if (g_gs_tri_rb1 == 8) hipLaunchKernelGGL((tri_gemm_kernel<1, 8>), dim3((unsigned)((rb + 7) / 8), ncolv), dim3(kThreads), 0, st, Xk, (const real*)(g->blk_s + r0), x + r0, rb, backward ? 1 : 0, (int64_t)g->n, (int64_t)g->n);
+      if (ncolv % 8 == 0) hipLaunchKernelGGL((tri_gemm_kernel<8, RB>), dim3(rgrid, ncolv / 8), dim3(kThreads), 0, st, Xk, (const real*)(g->blk_s + r0), x + r0, rb, backward ? 1 : 0, (int64_t)g->n, (int64_t)g->n);
+      else if (ncolv % 4 == 0) hipLaunchKernelGGL((tri_gemm_kernel<4, RB>), dim3(rgrid, ncolv / 4), dim3(kThreads), 0, st, Xk, (const real*)(g->blk_s + r0), x + r0, rb, backward ? 1 : 0, (int64_t)g->n, (int64_t)g->n);
+      else if (ncolv % 2 == 0) hipLaunchKernelGGL((tri_gemm_kernel<2, RB>), dim3(rgrid, ncolv / 2), dim3(kThreads), 0, st, Xk, (const real*)(g->blk_s + r0), x + r0, rb, backward ? 1 : 0, (int64_t)g->n, (int64_t)g->n);
       else hipLaunchKernelGGL(tri_gemv_kernel<1>, dim3((unsigned)rb, ncolv), dim3(kThreads), 0, st, Xk, (const real*)(g->blk_s + r0), x + r0, rb, backward ? 1 : 0, (int64_t)g->n, (int64_t)g->n);
     }
     HIP_TRY(hipGetLastError());
@@ -715,7 +701,7 @@ int csr_gs_sweep(amgh_csr* op, bool backward, bool sor, real omega, real* x, con
   int64_t ldb = g->n;
   if (first) g->s_dir = -1;
   if (lay != g) {
-    const bool flip = g->ncols == g->n && g->diag_nonzero && both_dirs && g_gs_flip &&
+    const bool flip = g->ncols == g->n && g->diag_nonzero && both_dirs &&
                       g->s_dir == (backward ? 0 : 1) && g->s_key == s_key;
     if (flip) {
       // the previous sweep of this smooth! call ran the other way on the same xp: s follows without a matrix pass
@@ -792,8 +778,11 @@ int csr_gs_sweep(amgh_csr* op, bool backward, bool sor, real omega, real* x, con
         if (dict) { fa.crec = g->bw.flow.crec; fa.dict = g->bw.flow.dict; fa.dict_ent = g->bw.flow.dict_ent; }
         e = bw::sweep_relay<real>(fa, g->bw.maxk, dict ? g->bw.flow.dict_lds : g->bw.flow.lds_max, sor, backward, st, BW_RELAY_W);
       } else if (ncolv == 1 && g_gs_bw_relay > 0) {
-        // (the persistent grid pays on the plain 19-point records only: 0.98 -> 0.87 ms there, 0.776 -> 0.787 on the dictionary layout)
-        fa.grid = g->bw.maxk > 6 ? (dict ? 0 : g_gs_bw_grid_long) : g_gs_bw_grid;
+        // workgroups of the sweep: one per block (0), or fewer on levels with rows of more than 6 entries ON PLAIN RECORDS — the persistent
+        // form of gs_relay.hpp (critical-path bound: fewer resident blocks, faster hand-offs).  The persistent grid pays on the plain
+        // 19-point records only: 0.98 -> 0.87 ms there, 0.776 -> 0.787 on the dictionary layout
+        constexpr int kBwGrid = 0, kBwGridLong = 512;
+        fa.grid = g->bw.maxk > 6 ? (dict ? 0 : kBwGridLong) : kBwGrid;
         fa.late = (g->bw.flow.late_ok && !g_gs_bw_inorder) ? 1 : 0;   // the dependency-aware row sum (gs_relay.hpp, LATE)
         if (dict) { fa.crec = g->bw.flow.crec; fa.dict = g->bw.flow.dict; fa.dict_ent = g->bw.flow.dict_ent; }
         e = bw::sweep_relay<real>(fa, g->bw.maxk, dict ? g->bw.flow.dict_lds : g->bw.flow.lds_max, sor, backward, st, BW_RELAY_W);
@@ -822,10 +811,7 @@ int csr_gs_sweep(amgh_csr* op, bool backward, bool sor, real omega, real* x, con
     g->xil_cols = ncolv;
   }
   const int ns = (int)lay->segs.size();
-  // (g_gs_dup_launch: measurement hook — every group launched 1 + that many times: a group's launch is idempotent, the
-  // repeats find its arrays in cache: what a prefetch of the next group's arrays could win at most)
-  for (int kk = 0; kk < ns * (1 + g_gs_dup_launch); ++kk) {
-    const int k = kk / (1 + g_gs_dup_launch);
+  for (int k = 0; k < ns; ++k) {
     const GsSchedule::Seg& s = lay->segs[backward ? ns - 1 - k : k];
     if (s.chain) {
       ChainArgs c{};
@@ -863,7 +849,7 @@ int csr_gs_sweep(amgh_csr* op, bool backward, bool sor, real omega, real* x, con
       const int nwg = (s.sell_nchunks + 3) / 4;
       // XCD-contiguous workgroup mapping only where a launch has several workgroups per CU: below that there is no re-use
       // to win and the mapping unbalances the XCDs (the 228 538-row level of the 256^3 hierarchy: 1.40 -> 1.29 ms per pass)
-      la.xcd_map = (g_gs_xcd_map && nwg >= 768) ? 1 : 0;
+      la.xcd_map = nwg >= 768 ? 1 : 0;
       const int grid = la.xcd_map ? ((nwg + kNumXcd - 1) / kNumXcd) * kNumXcd : nwg;
       if (il && sell_il_shape(s.sell_k, ncolv)) {
         SellIlArgs ia{};
@@ -877,12 +863,12 @@ int csr_gs_sweep(amgh_csr* op, bool backward, bool sor, real omega, real* x, con
       RC_TRY(launch_sell(la, sor, s.sell_k, grid, ncolv, st));
       HIP_TRY(hipGetLastError());
       if (il) RC_TRY(il_copy_rows(ncolv, xp, xs, g->xil, la.row0, la.nrows, st));
-    } else if (s.nslots > 0 && (g_gs_slots || lay->compacted)) {
+    } else if (s.nslots > 0) {
       SlotArgs sa{};
       sa.wcol = lay->wcol; sa.wval = lay->wval; sa.slot_row = lay->slot_row; sa.wmeta = lay->wmeta;
       sa.diag = lay->diag; sa.bp = rhs; sa.x = xp; sa.omega = omega; sa.slot0 = s.slot0;
       // (XCD-contiguous mapping only for launches of several workgroups per CU, as for the SELL launches above)
-      const bool xmap = g_gs_xcd_map && (s.nslots >= 768 || ncolv > 1);
+      const bool xmap = s.nslots >= 768 || ncolv > 1;
       sa.nslots = s.nslots; sa.xcd_map = xmap ? 1 : 0;
       sa.ldx = xs; sa.ldb = ldb;
       if (lay->slot_entries == kBigSlot) {  // long composite rows: 2048-entry slots, 8 lanes per row
@@ -898,7 +884,7 @@ int csr_gs_sweep(amgh_csr* op, bool backward, bool sor, real omega, real* x, con
         SlotIlArgs ia{};
         ia.wcol = sa.wcol; ia.wval = sa.wval; ia.slot_row = sa.slot_row; ia.wmeta = sa.wmeta; ia.diag = sa.diag;
         ia.xil = g->xil; ia.x = xp; ia.omega = omega; ia.slot0 = s.slot0; ia.nslots = s.nslots;
-        ia.xcd_map = (g_gs_xcd_map && s.nslots >= 768) ? 1 : 0;
+        ia.xcd_map = s.nslots >= 768 ? 1 : 0;
         ia.soff = (int32_t)g->ncols; ia.ldx = xs;
         const int grid = ia.xcd_map ? ((s.nslots + kNumXcd - 1) / kNumXcd) * kNumXcd : s.nslots;
         RC_TRY(launch_slot_il(ia, sor, ncolv, grid, st));

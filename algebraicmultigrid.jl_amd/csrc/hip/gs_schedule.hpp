@@ -1235,6 +1235,12 @@ int bw_build(GsSchedule* g, int64_t n, int64_t ncols, const int32_t* rowptr, con
   return AMGH_OK;
 }
 
+// operators below this many rows keep the level schedules in mode 1 (half as many for rows of at most 7 entries).  Round 3
+// (chained kernel): 3 000 000; with the relayed dataflow sweep and its own cost model (Plan::est_flow_seconds) the block layout
+// wins wherever that model says so: 48^3 ... 160^3 Poisson hierarchies -19 ... -28 % per V-cycle with the second level on it
+// too (profiles/r05_block_layout_threshold.log)
+constexpr int64_t kGsBwMinRows = 30000;
+
 // nrhs_hint: right-hand-side columns the sweeps of this schedule will carry (0 = unknown: the level schedules, which serve
 // any block size at its best known cost); the wavefront of blocks is chosen for single columns and — as a dataflow, whose
 // workgroups carry up to 8 columns past one record stream — for blocks of right-hand sides
@@ -1246,8 +1252,8 @@ int gs_build(GsSchedule* g, int64_t nrows, int64_t ncols, const int32_t* rowptr,
   // (size thresholds measured with the chained kernel, profiles/r03_bw_threshold.log: 7-point rows pay from ~1.5 M rows — 128^3:
   // 7.38 -> 7.22 ms per cycle, 96^3: 4.40 -> 4.52 —, 19-point rows from ~3 M — the 2.0 M-row second level of 160^3: 9.95 -> 10.51 ms)
   const int64_t n_level = std::max<int64_t>(n, tl_gs_level_rows);
-  bool bw_size_ok = n_level >= g_gs_bw_min_rows;
-  if (!bw_size_ok && n_level >= g_gs_bw_min_rows / 2 && n > 0 && rowptr[n] <= 7 * n) bw_size_ok = true;
+  bool bw_size_ok = n_level >= kGsBwMinRows;
+  if (!bw_size_ok && n_level >= kGsBwMinRows / 2 && n > 0 && rowptr[n] <= 7 * n) bw_size_ok = true;
   if (g_gs_bw > 0 && (nrhs_hint == 1 || (nrhs_hint > 1 && g_gs_bw_nrhs)) && n > 0 && (g_gs_bw == 2 || bw_size_ok)) {
     const int rcb = bw_build(g, n, ncols, rowptr, col, val, tm, nrhs_hint);
     if (rcb != AMGH_OK) return rcb;
@@ -1386,7 +1392,6 @@ int gs_build(GsSchedule* g, int64_t nrows, int64_t ncols, const int32_t* rowptr,
     const int S = g->super > 0 ? g->super : std::max(1, g->nblk);
     const double block_cost = g->nblk * 5.9e-6 + 2.0 * ((g->nblk + S - 1) / S) * 3.5e-6;
     int chosen_m[2] = {1, 1}, chosen_cap[2] = {kSlot, kSlot};
-    const int force_m = (g_gs_merge_force > 1 && (g_gs_merge_force_maxn <= 0 || n <= g_gs_merge_force_maxn)) ? g_gs_merge_force : 0;
     const bool host_merge = getenv("AMGH_HOST_MERGE") != nullptr;  // the host construction (reference for the device one)
     if (!host_merge) {
       // Candidates are BUILT on the device (milliseconds each: gs_merge_dev.hpp) instead of estimated from a sample on
@@ -1413,12 +1418,11 @@ int gs_build(GsSchedule* g, int64_t nrows, int64_t ncols, const int32_t* rowptr,
         worse = 0;
         int64_t prev_max = 0;  // longest composite row of the previous (shallower) candidate: rows only grow with m
         int m_hi = std::min(g_gs_merge, kMergeMaxRounds);
-        if (force_m > 1) m_lo = m_hi = std::min(force_m, kMergeMaxRounds);   // measurement hook: exactly this depth
         for (int m = m_lo; m <= m_hi; ++m) {
           MergeDev md;
           // candidates are COST-MODEL builds: every stride-th group only (entries per row, longest row and growth are bulk
           // properties of a grouping) — all but one of them are thrown away; the chosen one is built in full below
-          const int stride = (force_m > 1 || !g_gs_sample) ? 1 : std::max(1, std::min(8, ((g->nlev + m - 1) / m) / 12));
+          const int stride = std::max(1, std::min(8, ((g->nlev + m - 1) / m) / 12));
           rc2 = merge_build_dev(g, d_lev_of, g->diag, MergeGrouping::uniform(g->nlev, m, backward), &md,
                                 prev_max > 440 ? 2 : prev_max > 110 ? 1 : 0, stride);
           prev_max = md.max_row;
@@ -1454,7 +1458,7 @@ int gs_build(GsSchedule* g, int64_t nrows, int64_t ncols, const int32_t* rowptr,
             fprintf(stderr, "[amghip] n=%lld %s merge m=%d: %d groups, %.1f entries/row (max %lld), est. %.2f ms vs %.2f ms\n",
                     (long long)n, backward ? "bwd" : "fwd", m, ngrp, (double)md.total / n, (long long)md.max_row, 1e3 * c, 1e3 * best);
           const bool stream_bound = 12.0 * (double)md.total / 2.5e12 > best;  // streaming the composite rows alone costs more
-          if (c < 0.97 * best || force_m > 1) {
+          if (c < 0.97 * best) {
             best = c; chosen_m[dir] = m; chosen_cap[dir] = cap; worse = 0;
             chosen[dir].free_dev();
             chosen[dir] = std::move(md);
@@ -1482,7 +1486,7 @@ int gs_build(GsSchedule* g, int64_t nrows, int64_t ncols, const int32_t* rowptr,
       // when the per-group cost model says they win.  Measured (profiles/r02_zone_sweep.log): -12 % launches on the two
       // finest levels for -3 % sweep time; pricing a launch higher (deeper middle) LOSES: the long composite rows of deep
       // groups cost more than the launches they save.
-      for (int dir = 0; dir < 2 && rc2 == AMGH_OK && use && g_gs_zone && force_m <= 1; ++dir) {
+      for (int dir = 0; dir < 2 && rc2 == AMGH_OK && use; ++dir) {
         const bool backward = dir == 1;
         if (chosen_m[dir] <= 1 || chosen[dir].failed) continue;
         const int depth_cap = std::min(g_gs_merge, kMergeMaxRounds);
@@ -1501,10 +1505,11 @@ int gs_build(GsSchedule* g, int64_t nrows, int64_t ncols, const int32_t* rowptr,
         // the constants of merge_cost (fitted on whole sweeps of all levels): per byte they are pessimistic for the fine
         // level (its gathers are regular, ~5 TB/s while streaming) and right for the coarser ones (~2.6 TB/s) — a per-entry
         // price that is too LOW deepens the middle of a sweep and loses (measured: 32.1 -> 34.1 ms with 6 us + 4.8 TB/s)
-        // and below ~6 MB a launch does not get cheaper any more: 4.7 us of kernel + the boundary (the same probe)
-        const double t0 = 1e-9 * g_gs_zone_t0_ns, bsec = 12.0 / 2.5e12, floor_s = 1e-9 * g_gs_zone_floor_ns;
+        // and below ~6 MB a launch does not get cheaper any more: 4.7 us of kernel + the boundary (the same probe) — a floor the
+        // model leaves out.  t0: the price of a launch, 3 000 ns
+        const double t0 = 1e-9 * 3000, bsec = 12.0 / 2.5e12;
         auto group_cost = [&](int64_t entries, bool big) {
-          return std::max(floor_s, t0 + bsec * (double)entries) + (big ? 2.5e-6 : 0.0);
+          return t0 + bsec * (double)entries + (big ? 2.5e-6 : 0.0);
         };
         auto sweep_cost = [&](const MergeDev& md, const MergeGrouping& G, bool big) {
           double c = 0.0;
@@ -1536,7 +1541,7 @@ int gs_build(GsSchedule* g, int64_t nrows, int64_t ncols, const int32_t* rowptr,
             const double rows = (double)(base.lvl_ptr[l + 1] - base.lvl_ptr[l]);
             double bestc = 1e300;
             for (int d = 1; d <= cap_try; ++d) {
-              const double c = std::max(floor_s, t0 + bsec * rows * d * fl[d]) / d;
+              const double c = (t0 + bsec * rows * d * fl[d]) / d;
               if (c < bestc * (1.0 - 1e-9)) { bestc = c; want[sidx] = d; }
             }
             want[sidx] = std::max(want[sidx], std::min(chosen_m[dir], cap_try));   // never shallower than the uniform choice

@@ -175,7 +175,7 @@ int amgh_num_levels(const amgh_t* h);            /* length(ml.levels)           
  * x += P * coarse_x — so from the first level with at most `tail_dense_rows` rows (tunable, default 6144; 0 = off; read at
  * amgh_finalize) down, __solve_next! (multilevel.jl:200-212) IS one dense n x n operator per cycle type (V / W / F), and the
  * cycle applies it in ONE launch.  The operator is built from the library's own recursion on the columns of the identity
- * (blocks of `tail_dense_batch` right-hand sides, default 64), either by this call or by the first cycle of that type; a hierarchy whose
+ * (blocks of 64 right-hand sides), either by this call or by the first cycle of that type; a hierarchy whose
  * finest level is that small is one operator altogether (a cycle on a non-zero x: x += M (b - A x), the same iteration).
  * Results: the per-level cycle's up to the rounding of an n-term sum (tests: <= 1e-12 relative).  Not built with a host coarse
  * solver (amgh_set_coarse_host).  Tunable "tail_dense" = 0 (read at every cycle) runs the levels one by one again.
@@ -573,30 +573,39 @@ int amgh_debug_bw_late(const amgh_t* h, int l);
  * (prolongation, :233-234).  -1: no such level.                                                                       */
 int amgh_debug_coded_ops(const amgh_t* h, int l);
 
-/* Diagnostics: tunables of the Gauss-Seidel execution (process-wide; used by tools/ to pick the defaults and by
- * tests to force every path).  Read at every sweep: "gs_xcd_map", "gs_block_pipe", "gs_flip", "gs_keep_lo",
- * "gs_slots", "gs_block_target", "gs_min_rows", "gs_threads", "gs_nnz_per_wg", "gs_tiny" (operators that fit LDS
- * entirely: 1 = walked by a single wave from their packed record where one was built, else the whole-operator chain
- * kernel; 2 = the whole-operator chain kernel; 0 = the regular chain kernel — all three bitwise the same sweep),
- * "jacobi_zero", "rhs_il", and "gs_merge" <= 1 /
- * "gs_block_inverse" = 0 to bypass already-built merged groups / block-inverse data.  Read when a schedule is BUILT
- * (amgh_push_level, first stand-alone sweep of an operator): "gs_merge" (largest group of dependency levels tried),
- * "gs_bigslot" (0 off, 1 cost model, 2 always), "gs_super" (blocks per superblock), "gs_block_inverse", "gs_bw" (the
- * wavefront-of-blocks layout of single-column hierarchies: 0 off, 1 where its cost model prefers it, 2 always),
- * "gs_bw_rows" (rows per block aimed at, 512), "gs_bw_min_rows" (smallest operator considered in mode 1: 30 000 rows, half of it for operators of at most 7 entries per row — above it the cost model decides);
- * "gs_bw_two_min_rows" (operators with TWO offset classes — 2-D grids — take that layout from this many rows: 200 000;
- * 0 never), "gs_bw_nrhs" (1: hierarchies created for blocks of right-hand sides get it too, on structurally symmetric
- * levels), "gs_bw_flow" (1: the dataflow layout of the wavefront is built where the pattern is structurally symmetric);
- * read at every sweep: "gs_bw_flow" (0: the chained / launched execution where its layout was kept), "gs_bw_chain" (1: the
- * wavefront of blocks as ONE launch per sweep, blocks chained by flags; 0: one launch per depth of the quotient graph —
- * bitwise the same sweep), "gs_bw_nc" (columns of a block of right-hand sides one workgroup of the dataflow sweep carries: -1 = 3 on the dictionary layout, 2 on plain records;
- * 0 = as many as are instantiated), "gs_bw_spin" / "gs_bw_skip_pub" (test hooks: bound of a poll, a block that publishes
- * nothing), "gs_flow_xzero" (1: a dataflow sweep that starts a smooth! call on x = 0 reads no x — bitwise the same),
- * "gs_bw_dict" (1: dataflow schedules carry the dictionary layout where the rows' values repeat — at most 256 distinct
- * value rows per block, a quarter of the rows overall — and the relayed and the multi-column sweeps read it, bitwise the
- * same; read at build and at every sweep),
- * "stream_code" (1: value-coded columns, see amgh_debug_coded_ops; read at amgh_finalize and at every launch),
- * "gs_dup_launch" (measurement hook: every merged-group launch issued 1 + that many times).
+/* Diagnostics: tunables of the Gauss-Seidel execution and the cycle (process-wide; used by tools/ to pick the defaults and
+ * by tests to force every path).  Read at every sweep: "gs_block_pipe", "gs_tiny" (operators that fit LDS entirely: 1 =
+ * walked by a single wave from their packed record where one was built, else the whole-operator chain kernel; 2 = the
+ * whole-operator chain kernel; 0 = the regular chain kernel — all three bitwise the same sweep), "gs_wave_quad" (1: the
+ * single-wave walk with four lanes per row where its record was built; 0: one lane per row, the scalar loop's bits),
+ * "gs_lpr" / "gs_ept" (lanes per row / entries per thread of merged slot launches, 0 = by shape), "gs_il" (blocks of
+ * right-hand sides: merged groups gather from an interleaved copy), "gs_sell" (merged groups from the SELL-like layout),
+ * "gs_dense_tri" (small operators through the dense inverse of the whole triangle), "jacobi_zero", "rhs_il", and
+ * "gs_merge" <= 1 / "gs_block_inverse" = 0 to bypass already-built merged groups / block-inverse data.  Read when a
+ * schedule is BUILT (amgh_push_level, first stand-alone sweep of an operator): "gs_merge" (largest group of dependency
+ * levels tried), "gs_bigslot" (0 off, 1 cost model, 2 always), "gs_super" (blocks per superblock), "gs_block_inverse",
+ * "gs_dense_tri", "gs_dense_blk" (rows per dense block above the whole-triangle size), "gs_sell", "gs_lean" (footprint
+ * policy: -1 = the AMGH_LEAN environment variable, 0 full, 1 lean, 2 trim), "gs_bw" (the wavefront-of-blocks layout of
+ * single-column hierarchies: 0 off, 1 where its cost model prefers it, 2 always), "gs_bw_rows" (rows per block aimed at,
+ * 512), "gs_bw_two_min_rows" (operators with TWO offset classes — 2-D grids — take that layout from this many rows:
+ * 200 000; 0 never), "gs_bw_nrhs" (1: hierarchies created for blocks of right-hand sides get it too, on structurally
+ * symmetric levels), "gs_bw_flow" (1: the dataflow layout of the wavefront is built where the pattern is structurally
+ * symmetric); read at every sweep: "gs_bw_flow" (0: the chained / launched execution where its layout was kept),
+ * "gs_bw_chain" (1: the wavefront of blocks as ONE launch per sweep, blocks chained by flags; 0: one launch per depth of
+ * the quotient graph — bitwise the same sweep), "gs_bw_nc" (columns of a block of right-hand sides one workgroup of the
+ * dataflow sweep carries: -1 = 3 on the dictionary layout, 2 on plain records; 0 = as many as are instantiated),
+ * "gs_bw_relay" (0: one walker per block instead of the relayed walk — bitwise the same), "gs_bw_inorder" (1: the relayed
+ * sweep sums every row in stored entry order, see amgh_debug_bw_late), "gs_bw_spin" / "gs_bw_skip_pub" (test hooks:
+ * bound of a poll, a block that publishes nothing), "gs_flow_xzero" (1: a dataflow sweep that starts a smooth! call on
+ * x = 0 reads no x — bitwise the same), "gs_bw_dict" (1: dataflow schedules carry the dictionary layout where the rows'
+ * values repeat — at most 256 distinct value rows per block, a quarter of the rows overall — and the relayed and the
+ * multi-column sweeps read it, bitwise the same; read at build and at every sweep).  Read at amgh_push_level:
+ * "gs_coarse_lo" (1: a level hands its coarse vectors over in the next level's order).  Read at amgh_finalize:
+ * "tail_dense_rows" (the collapsed coarse tail: the first level with at most this many rows and everything below it
+ * become one dense operator; 0 off), "trim_coded" (operators with value-coded columns keep only them), and at every
+ * cycle "tail_dense" (0: the per-level cycle instead of the built tail); "stream_code" (1: value-coded columns, see
+ * amgh_debug_coded_ops; read at amgh_finalize and at every launch); "pcg_fused" (amgh_pcg: 1 = the fused recurrence,
+ * 0 = one launch per operation — bitwise the same iterates).
  * Returns AMGH_EINVAL for an unknown name.                                                                       */
 int amgh_debug_set_tunable(const char* name, int value);
 

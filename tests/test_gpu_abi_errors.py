@@ -276,5 +276,11 @@ def test_setup_entry_points_reject_bad_arguments():
     assert lib.amgh_setup_fit_candidates_vector(dA.h, b.ctypes.data, 1e-10, None, bc.ctypes.data) == -2
     assert lib.amgh_setup_fit_candidates_vector(None, b.ctypes.data, 1e-10, C.byref(out), bc.ctypes.data) == -2
     assert lib.amgh_debug_set_tunable(b"gs_bw_nc", -1) == 0 and lib.amgh_debug_set_tunable(b"no_such_tunable", 1) == -2
+    # retired tunables (their shipped values are constants now): rejected like any unknown name, no state changed
+    for name in ("gs_block_target", "gs_min_rows", "gs_nnz_per_wg", "gs_threads", "gs_slots", "gs_xcd_map", "gs_tri_rb",
+                 "gs_tri_rb1", "gs_dti_pre", "stream_xcd", "tail_dense_batch", "gs_sample", "gs_merge_force",
+                 "gs_merge_force_maxn", "gs_zone", "gs_zone_t0_ns", "gs_zone_floor_ns", "gs_flip", "gs_keep_lo",
+                 "gs_dup_launch", "gs_bw_min_rows", "gs_bw_grid", "gs_bw_grid_long"):
+        assert lib.amgh_debug_set_tunable(name.encode(), 1) == -2, name
     h = C.c_void_p()
     assert lib.amgh_create(C.byref(h), 0, 65) != 0 and lib.amgh_create(C.byref(h), 0, 0) != 0      # 1 <= nrhs <= 64

@@ -46,4 +46,4 @@ for st in settings:
     z = run(devb, bs, st)
     if zref is None: zref = z
     print(f"    max rel. difference from the first setting {np.abs(z - zref).max() / np.abs(zref).max():.2e}; bitwise {bool((z == zref).all())}", flush=True)
-    for k, v in pairs: devb.lib.amgh_debug_set_tunable(k.encode(), {"gs_il": 1, "gs_tri_rb": 1}.get(k, 0))
+    for k, v in pairs: devb.lib.amgh_debug_set_tunable(k.encode(), {"gs_il": 1}.get(k, 0))

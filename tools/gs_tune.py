@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Smoother-pass time per level for several settings of the SWEEP-time tunables (amgh_debug_set_tunable:
-gs_xcd_map, gs_block_pipe, gs_flip, gs_slots, gs_nnz_per_wg, gs_block_target, ...) on one resident hierarchy.
+gs_block_pipe, gs_tiny, gs_lpr, gs_ept, gs_il, ...) on one resident hierarchy.
 Tunables that are read when a schedule is built (gs_merge, gs_super, gs_bigslot, gs_block_inverse) need
 tools/tunable_sweep.py instead.
 usage: python tools/gs_tune.py [N=256] [name=v[,name=v...] ...]      each argument = one configuration"""
@@ -8,7 +8,7 @@ import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import amg_amd as AMG
 N = int(sys.argv[1]) if len(sys.argv) > 1 else 256
-configs = sys.argv[2:] or ["gs_xcd_map=0", "gs_xcd_map=1"]
+configs = sys.argv[2:] or ["gs_block_pipe=0", "gs_block_pipe=1"]
 A = AMG.poisson((N, N, N)); ml = AMG.ruge_stuben(A); dev = ml.device(); lib = dev.lib
 print("levels", [l.A.m for l in ml.levels])
 lv = [l for l in range(len(ml.levels)) if ml.levels[l].A.m >= 256]

@@ -24,7 +24,6 @@ def run(tag, sets):
 run("default", [])
 run("gs_bw=0", [(b"gs_bw", 0)])
 run("gs_bw=0 lean=0", [(b"gs_lean", 0)])
-run("gs_bw=0 lean=0 xcd=0", [(b"gs_xcd_map", 0)])
-run("gs_bw=0 lean=0 xcd=1 tiny=0", [(b"gs_xcd_map", 1), (b"gs_tiny", 0)])
+run("gs_bw=0 lean=0 tiny=0", [(b"gs_tiny", 0)])
 run("gs_bw=0 lean=0 tiny=2", [(b"gs_tiny", 2)])
 run("gs_bw=0 lean=0 tiny=1 lpr=1", [(b"gs_tiny", 1), (b"gs_lpr", 1)])

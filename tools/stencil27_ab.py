@@ -14,7 +14,6 @@ M = (27.0 * sp.identity(s ** 3) - sp.kron(sp.kron(S, S), S)).tocsc()
 A = AMG.SparseMatrixCSC.from_scipy(M); n = A.m
 t0 = time.perf_counter(); ml = AMG.ruge_stuben(A); ts = time.perf_counter() - t0
 print(f"27-point {s}^3 n={n} nnz={M.nnz} levels {[l.A.m for l in ml.levels]} setup {ts:.1f}s", flush=True)
-lib.amgh_debug_set_tunable(b"gs_bw_min_rows", 1000000)
 for bw in (0, 1, 2):
     lib.amgh_debug_set_tunable(b"gs_bw", bw)
     dev = DeviceHierarchy(ml, 0, 1)
