@@ -147,6 +147,7 @@ def _bind_solve_phase(L, creal, coarse_fn):
     L.amgh_level_residual_d.argtypes = [vp, C.c_int, vp, vp, vp]
     L.amgh_level_smooth.argtypes = [vp, C.c_int, C.c_int, vp, vp]
     L.amgh_level_smooth_d.argtypes = [vp, C.c_int, C.c_int, vp, vp]
+    L.amgh_debug_level_smooth_block_d.argtypes = [vp, C.c_int, C.c_int, vp, vp]
     L.amgh_csr_create.argtypes = [C.POINTER(vp), C.c_int, i64, i64, vp, vp, vp]
     L.amgh_csr_destroy.argtypes = [vp]
     L.amgh_csr_destroy.restype = None
@@ -181,6 +182,7 @@ def _bind_solve_phase(L, creal, coarse_fn):
     L.amgh_debug_bw_sweep_host.argtypes = [i64, vp, vp, vp, C.c_int, C.c_int, C.c_double, vp, vp, vp]
     L.amgh_debug_bw_dict_sweep_host.argtypes = [i64, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp]
     L.amgh_debug_set_tunable.argtypes = [C.c_char_p, C.c_int]
+    L.amgh_debug_get_tunable.argtypes = [C.c_char_p, C.POINTER(C.c_int)]
     L.amgh_profile_enable.argtypes = [vp, C.c_int]
     L.amgh_profile_read.argtypes = [vp, vp, C.c_int]
     L.amgh_set_use_graph.argtypes = [vp, C.c_int]

@@ -83,7 +83,8 @@ struct amgh_handle {
   std::vector<double> prof_ms;
   struct Ev { hipEvent_t a, b; int label, level; };
   std::vector<Ev> pending;
-  hipEvent_t t0 = nullptr, t1 = nullptr;
+  hipEvent_t t0 = nullptr, t1 = nullptr;   // amgh_timer_begin / amgh_timer_end: the caller's region, nothing else records them
+  hipEvent_t tb0 = nullptr, tb1 = nullptr; // the library's own timings inside a call (tail_dense_build, amgh_bench_op)
   // Measured on MI355X (profiles/r01_vcycle_profile.log): replaying a 256^3 V-cycle (~11k kernel
   // nodes) from a hipGraph takes 180.1 ms vs 179.6 ms eager — the cycle is bound by the GPU-side
   // latency of each dependency-level kernel, not by host launches — and rocprofv3's kernel tracing
@@ -400,7 +401,7 @@ int tail_dense_build(amgh_t* h, int cyc) {
   const int64_t n = L0->n;
   const int BB = h->tail_cols;
   if (BB < 1 || BB > 64) return AMGH_ESTATE;
-  HIP_TRY(hipEventRecord(h->t0, h->stream));
+  HIP_TRY(hipEventRecord(h->tb0, h->stream));
   real *X = nullptr, *B = nullptr, *Mc = nullptr, *M = nullptr;
   auto cleanup = [&] { hipFree(X); hipFree(B); hipFree(Mc); };
   int rc = dev_alloc(&X, n * BB);
@@ -432,8 +433,8 @@ int tail_dense_build(amgh_t* h, int cyc) {
     }
   }
   float ms = 0.f;
-  if (rc == AMGH_OK && (hipEventRecord(h->t1, h->stream) != hipSuccess || hipEventSynchronize(h->t1) != hipSuccess ||
-                        hipEventElapsedTime(&ms, h->t0, h->t1) != hipSuccess)) rc = -1001;
+  if (rc == AMGH_OK && (hipEventRecord(h->tb1, h->stream) != hipSuccess || hipEventSynchronize(h->tb1) != hipSuccess ||
+                        hipEventElapsedTime(&ms, h->tb0, h->tb1) != hipSuccess)) rc = -1001;
   if (rc != AMGH_OK) { hipStreamSynchronize(h->stream); cleanup(); hipFree(M); (void)hipGetLastError(); return rc; }
   cleanup();
   h->tail[cyc].M = M;
@@ -810,6 +811,8 @@ int amgh_create(amgh_t** hp, int device, int nrhs) {
   if (e != hipSuccess) { delete h; return -(1000 + (int)e); }
   hipEventCreate(&h->t0);
   hipEventCreate(&h->t1);
+  hipEventCreate(&h->tb0);
+  hipEventCreate(&h->tb1);
   if (const char* e = getenv("AMGH_USE_GRAPH")) { h->use_graph = (e[0] == '1'); h->graph_auto = false; }
   *hp = h;
   return AMGH_OK;
@@ -837,6 +840,8 @@ void amgh_destroy(amgh_t* h) {
   for (auto& g : h->graphs) if (g.exec) hipGraphExecDestroy(g.exec);
   if (h->t0) hipEventDestroy(h->t0);
   if (h->t1) hipEventDestroy(h->t1);
+  if (h->tb0) hipEventDestroy(h->tb0);
+  if (h->tb1) hipEventDestroy(h->tb1);
   if (h->own_stream) hipStreamDestroy(h->own_stream);
   else if (h->stream) hipStreamDestroy(h->stream);
   delete h;
@@ -1793,6 +1798,23 @@ int amgh_level_smooth_d(amgh_t* h, int level, int post, real* x_d, const real* b
   return bw_err_check();
 }
 
+// The level's smoother on ALL columns of the handle's block (x_d, b_d: n x nrhs, column-major), as the cycle launches it
+// (smooth with ncolv = nrhs: the multi-column sweeps); amgh_level_smooth(_d) sweep one column.
+int amgh_debug_level_smooth_block_d(amgh_t* h, int level, int post, real* x_d, const real* b_d) {
+  RC_TRY(check_ready(h));
+  if (level < 0 || level >= (int)h->levels.size() || !x_d || !b_d) return AMGH_EINVAL;
+  HIP_TRY(hipSetDevice(h->device));
+  Level* L = h->levels[level];
+  const amgh_smoother_t& s = post ? L->post : L->pre;
+  if (s.kind == AMGH_SMOOTH_JACOBI && !L->tmp) return AMGH_ESTATE;
+  real* xc = x_d;
+  real* xo = L->tmp;
+  RC_TRY(smooth(h, L, s, xc, xo, b_d, h->nrhs));
+  if (xc != x_d) RC_TRY(vec_copy(h, x_d, xc, L->n * h->nrhs));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  return bw_err_check();
+}
+
 int amgh_level_smooth(amgh_t* h, int level, int post, real* x, const real* b) {
   RC_TRY(check_ready(h));
   if (level < 0 || level >= (int)h->levels.size() || !x || !b) return AMGH_EINVAL;
@@ -1994,12 +2016,12 @@ int amgh_bench_op(amgh_t* h, int level, int which, int reps, int warmup, double*
   };
   for (int i = 0; i < warmup && rc == AMGH_OK; ++i) rc = run();
   if (rc == AMGH_OK) {
-    hipEventRecord(h->t0, h->stream);
+    hipEventRecord(h->tb0, h->stream);
     for (int i = 0; i < reps && rc == AMGH_OK; ++i) rc = run();
-    hipEventRecord(h->t1, h->stream);
-    hipEventSynchronize(h->t1);
+    hipEventRecord(h->tb1, h->stream);
+    hipEventSynchronize(h->tb1);
     float f = 0.f;
-    hipEventElapsedTime(&f, h->t0, h->t1);
+    hipEventElapsedTime(&f, h->tb0, h->tb1);
     *avg_ms = (double)f / reps;
   }
   hipFree(x); hipFree(y); hipFree(b);
@@ -2299,6 +2321,49 @@ int amgh_debug_set_tunable(const char* name, int value) {
   else if (!strcmp(name, "gs_block_pipe")) g_gs_block_pipe = value;
   else return AMGH_EINVAL;
   ++g_sched_epoch;   // captured cycles bake the execution path in: every handle captures again after a change
+  return AMGH_OK;
+}
+
+// The stored value of a tunable amgh_debug_set_tunable accepts (after its normalisation): what a caller needs to put the
+// state back exactly as it found it.
+int amgh_debug_get_tunable(const char* name, int* value) {
+  if (!name || !value) return AMGH_EINVAL;
+  if (!strcmp(name, "gs_block_inverse")) *value = g_gs_block_inverse;
+  else if (!strcmp(name, "gs_lpr")) *value = g_gs_lpr;
+  else if (!strcmp(name, "gs_il")) *value = g_gs_il;
+  else if (!strcmp(name, "trim_coded")) *value = g_trim_coded;
+  else if (!strcmp(name, "gs_wave_quad")) *value = g_gs_wave_quad;
+  else if (!strcmp(name, "pcg_fused")) *value = g_pcg_fused;
+  else if (!strcmp(name, "tail_dense_rows")) *value = g_tail_dense_rows;
+  else if (!strcmp(name, "tail_dense")) *value = g_tail_dense;
+  else if (!strcmp(name, "gs_lean")) *value = g_gs_lean;
+  else if (!strcmp(name, "gs_sell")) *value = g_gs_sell;
+  else if (!strcmp(name, "gs_tiny")) *value = g_gs_tiny;
+  else if (!strcmp(name, "gs_bw")) *value = g_gs_bw;
+  else if (!strcmp(name, "gs_bw_rows")) *value = g_gs_bw_rows;
+  else if (!strcmp(name, "gs_bw_chain")) *value = g_gs_bw_chain;
+  else if (!strcmp(name, "gs_bw_flow")) *value = g_gs_bw_flow;
+  else if (!strcmp(name, "gs_bw_spin")) *value = g_gs_bw_spin;
+  else if (!strcmp(name, "gs_bw_nc")) *value = g_gs_bw_nc;
+  else if (!strcmp(name, "gs_bw_nrhs")) *value = g_gs_bw_nrhs;
+  else if (!strcmp(name, "gs_bw_skip_pub")) *value = g_gs_bw_skip_pub;
+  else if (!strcmp(name, "gs_bw_two_min_rows")) *value = g_gs_bw_two_min_rows;
+  else if (!strcmp(name, "gs_flow_xzero")) *value = g_gs_flow_xzero;
+  else if (!strcmp(name, "gs_bw_dict")) *value = g_gs_bw_dict;
+  else if (!strcmp(name, "gs_bw_inorder")) *value = g_gs_bw_inorder;
+  else if (!strcmp(name, "stream_code")) *value = g_stream_code;
+  else if (!strcmp(name, "gs_bw_relay")) *value = g_gs_bw_relay;
+  else if (!strcmp(name, "rhs_il")) *value = g_rhs_il;
+  else if (!strcmp(name, "jacobi_zero")) *value = g_jacobi_zero;
+  else if (!strcmp(name, "gs_ept")) *value = g_gs_ept;
+  else if (!strcmp(name, "gs_merge")) *value = g_gs_merge;
+  else if (!strcmp(name, "gs_coarse_lo")) *value = g_gs_coarse_lo;
+  else if (!strcmp(name, "gs_dense_tri")) *value = g_gs_dense_tri;
+  else if (!strcmp(name, "gs_dense_blk")) *value = g_gs_dense_blk;
+  else if (!strcmp(name, "gs_bigslot")) *value = g_gs_bigslot;
+  else if (!strcmp(name, "gs_super")) *value = g_gs_super;
+  else if (!strcmp(name, "gs_block_pipe")) *value = g_gs_block_pipe;
+  else return AMGH_EINVAL;
   return AMGH_OK;
 }
 

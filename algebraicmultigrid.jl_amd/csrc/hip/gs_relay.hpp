@@ -71,9 +71,14 @@ __device__ __forceinline__ unsigned lds_addr(const void* p) { return (unsigned)(
 // so the half of the sum that multiplies the sweep's FAR side (x values nobody writes before this row is done: rows behind it
 // in a forward sweep, before it in a backward one) is gathered and summed ABOVE the hand-over, and only the near half — the
 // rows the previous steps and the predecessor blocks produce — is gathered and added below it: MAXK / 2 gathers, products and
-// dependent adds in the tail instead of MAXK (a wave pays ~3 ns per instruction, whatever it is).  Per row: early = sum of
-// the far half in stored order, acc = early + the near half in stored order — deterministic, the same Gauss-Seidel iterate,
-// not the scalar loop's bits (tunable gs_bw_inorder = 1 keeps those).
+// dependent adds in the tail instead of MAXK (a wave pays ~3 ns per instruction, whatever it is).  Per row: early = the far
+// half as a chain of fused multiply-adds in stored order; above the hand-over the row is brought to x_i = q0 + sum_near nv[k]
+// x[k] (Gauss-Seidel: q0 = (b - early) rc, nv[k] = -RN(v[k] rc), rc = RN(1 / d) from the record; SOR: q0 = (1 - omega) x_i +
+// (omega / d)(b - early), nv[k] = -RN(v[k] omega / d)); below it the near half is fused multiply-adds into q0, in two
+// interleaved chains joined by one add where MAXK / 2 >= 6.  Deterministic, the same Gauss-Seidel iterate, not the scalar
+// loop's bits (tunable gs_bw_inorder = 1 keeps those) and more than one reassociation: the pre-scaling rounds every near
+// product twice.  What holds per row, and tests/sweep_bound.py asserts: |x_i - x*_i| <= (m_i + 4) u (|omega| (|b_i| +
+// sum |a_ik x_k|) / |a_ii| + |1 - omega| |x_old,i|), x* the exact update from the same inputs, m_i the row's off-diagonals.
 template <typename R, bool SOR, bool BWD, int MAXK, int W, bool DICT, bool LATE>
 __device__ __forceinline__ void relay_block(const FlowArgs<R>& a, unsigned char* lds_all, const int wv, const int lane, const unsigned int ut,
                                             const unsigned int epoch, const long long t_start) {

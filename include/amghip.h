@@ -268,6 +268,9 @@ int amgh_level_residual_d(amgh_t* h, int level, const amgh_real* x_d, const amgh
  * 113-141, 193-221); post = 0 | 1                                               */
 int amgh_level_smooth(amgh_t* h, int level, int post, amgh_real* x, const amgh_real* b);
 int amgh_level_smooth_d(amgh_t* h, int level, int post, amgh_real* x_d, const amgh_real* b_d);
+/* ... on all nrhs columns of the handle's block (x_d, b_d: n x nrhs device arrays, column-major), as the cycle's smoother
+ * runs them (the multi-column sweeps); the two above sweep one column.  Diagnostics / tests.                       */
+int amgh_debug_level_smooth_block_d(amgh_t* h, int level, int post, amgh_real* x_d, const amgh_real* b_d);
 
 /* ------------------------------------------------------------------------- */
 /* Stand-alone CSR operators on HBM (used by the row-sharded multi-GPU driver,  */
@@ -561,10 +564,15 @@ int amgh_debug_bw_mode(const amgh_t* h, int l);
  * distinct value rows, held in LDS; tunable "gs_bw_dict"): 1 / 0, -1: no such level.                                */
 int amgh_debug_bw_dict(const amgh_t* h, int l);
 /* ... and whether its rows are summed with the sweep's FAR side above the hand-over (the relayed walk's dependency-aware row
- * sum: the entries of smoother.jl:81-87's sum whose x cannot change any more are added first, the near half behind the
- * hand-over — the same iterate, one reassociation per row; tunable "gs_bw_inorder" = 1 restores the stored-order sum, the
- * scalar loop's bits): 1 / 0, -1: no such level.  Needs records whose entries lie split around the padding with at most
- * half of the slots on either side (every non-sharded operator whose rows are that balanced).                         */
+ * sum: the entries of smoother.jl:81-87's sum whose x cannot change any more are summed first, the near half behind the
+ * hand-over; tunable "gs_bw_inorder" = 1 restores the stored-order sum, the scalar loop's bits): 1 / 0, -1: no such level.
+ * The same Gauss-Seidel / SOR iterate in another rounding, not one reassociation: above the hand-over early = the far half
+ * as a chain of fused multiply-adds and q0 = (b - early) * rc with rc = RN(1 / d) from the record (SOR: q0 = (1 - omega) x
+ * + (omega / d)(b - early)); below it x = q0 + sum of fma(-RN(v * rc), x_near) — in two interleaved chains joined by one
+ * add for rows of 12 or more slots.  Rows whose record asks for the division take (b - sum) / d.  Each row stays within
+ * (m + 4) u (|omega| (|b| + sum |a x|) / |d| + |1 - omega| |x_old|) of the exact row update (m its off-diagonal entries,
+ * u the unit roundoff), which the test suite asserts row by row.  Needs records whose entries lie split around the padding
+ * with at most half of the slots on either side (every non-sharded operator whose rows are that balanced).            */
 int amgh_debug_bw_late(const amgh_t* h, int l);
 /* Diagnostics: which operators of level l the level-ordered cycle streams as VALUE-CODED columns (one 32-bit word per
  * entry: column | code << 24, the code an index into the operator's table of distinct values — built at amgh_finalize for
@@ -608,6 +616,10 @@ int amgh_debug_coded_ops(const amgh_t* h, int l);
  * 0 = one launch per operation — bitwise the same iterates).
  * Returns AMGH_EINVAL for an unknown name.                                                                       */
 int amgh_debug_set_tunable(const char* name, int value);
+/* The stored value of a tunable: the names amgh_debug_set_tunable accepts, the value after its normalisation (e.g.
+ * "tail_dense_rows" < 0 reads 0, the 0 / 1 switches read 0 or 1, "gs_bw_relay" reads the one instantiated count).
+ * Returns AMGH_EINVAL for any other name (the retired ones included).                                             */
+int amgh_debug_get_tunable(const char* name, int* value);
 
 /* Replay whole cycles from captured hipGraphs (default off: measured no gain on MI355X for big hierarchies —
  * the cycle is GPU-latency-bound and the host runs far ahead — nor for small ones, whose kernels take >= 3 us each;

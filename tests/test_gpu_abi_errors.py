@@ -282,5 +282,44 @@ def test_setup_entry_points_reject_bad_arguments():
                  "gs_merge_force_maxn", "gs_zone", "gs_zone_t0_ns", "gs_zone_floor_ns", "gs_flip", "gs_keep_lo",
                  "gs_dup_launch", "gs_bw_min_rows", "gs_bw_grid", "gs_bw_grid_long"):
         assert lib.amgh_debug_set_tunable(name.encode(), 1) == -2, name
+        v = C.c_int(12345)
+        assert lib.amgh_debug_get_tunable(name.encode(), C.byref(v)) == -2 and v.value == 12345, name
     h = C.c_void_p()
     assert lib.amgh_create(C.byref(h), 0, 65) != 0 and lib.amgh_create(C.byref(h), 0, 0) != 0      # 1 <= nrhs <= 64
+
+
+def test_tunable_getter_reads_back_what_the_setter_stored():
+    """amgh_debug_get_tunable accepts exactly the setter's names and returns the value after the setter's normalisation
+    (tail_dense_rows < 0 -> 0, the 0 / 1 switches -> 0 or 1, gs_bw_relay -> 0 or the one instantiated count); unknown
+    names, retired names and NULL arguments are AMGH_EINVAL.  Both instances of the library; every value put back."""
+    from shipping_defaults import TUNABLES
+    boolean = ("gs_bw_dict", "gs_bw_inorder", "stream_code")
+    for dt in ("float64", "float32"):
+        lib = AMG.hip_lib(dt)
+        saved = {}
+        for name in TUNABLES:
+            v = C.c_int(0)
+            assert lib.amgh_debug_get_tunable(name.encode(), C.byref(v)) == 0, (dt, name)
+            saved[name] = v.value
+        relay = saved["gs_bw_relay"]
+        assert relay > 0                                         # (the default: the relayed walk on)
+        try:
+            for name in TUNABLES:
+                for val in (0, 1, 7, -3, saved[name]):
+                    want = (max(val, 0) if name == "tail_dense_rows" else int(val != 0) if name in boolean
+                            else (relay if val != 0 else 0) if name == "gs_bw_relay" else val)
+                    assert lib.amgh_debug_set_tunable(name.encode(), val) == 0, (dt, name, val)
+                    v = C.c_int(12345)
+                    assert lib.amgh_debug_get_tunable(name.encode(), C.byref(v)) == 0, (dt, name)
+                    assert v.value == want, (dt, name, val, v.value)
+        finally:
+            for name, val in saved.items():
+                lib.amgh_debug_set_tunable(name.encode(), val)
+        for name, val in saved.items():
+            v = C.c_int(0)
+            assert lib.amgh_debug_get_tunable(name.encode(), C.byref(v)) == 0 and v.value == val, (dt, name)
+        v = C.c_int(0)
+        for bad in (b"no_such_tunable", b"", b"GS_BW", b"gs_bw ", b"gs_block_target", b"tail_dense_batch"):
+            assert lib.amgh_debug_get_tunable(bad, C.byref(v)) == EINVAL, bad
+        assert lib.amgh_debug_get_tunable(None, C.byref(v)) == EINVAL
+        assert lib.amgh_debug_get_tunable(b"gs_bw", None) == EINVAL

@@ -290,6 +290,17 @@ def test_blocks_of_right_hand_sides_on_the_dataflow_layout_equal_the_single_colu
     oh = O.OracleHierarchy(ml)
     for c in range(bs):
         assert np.array_equal(Z[:, c], singles[c]), (c, rel(Z[:, c], singles[c]))
+    if case.endswith("-sor"):
+        # the multi-column sweep itself (the level's forward SOR pre-smoother on the whole block, one launch): every column the
+        # oracle's sweep bit for bit and within the per-row bound of tests/sweep_bound.py
+        from sweep_bound import assert_sweep_within_bound, directional, smooth_block
+        pre = ml.levels[0].presmoother
+        X0 = np.stack([uniform(n, 90 + c) - 0.5 for c in range(bs)], axis=1)
+        with tunables(lib, gs_lpr=1, gs_ept=1):
+            XS = smooth_block(devb, 0, 0, X0, B)
+        for c in range(bs):
+            assert np.array_equal(XS[:, c], O.smooth(pre, A, X0[:, c], B[:, c], hermitian=True)), c
+            assert_sweep_within_bound(A, X0[:, c], B[:, c], XS[:, c], *directional(pre), what="block column %d" % c)
     assert np.array_equal(X[:, 0], x0)
     assert rel(Z[:, bs - 1], oh.precond(B[:, bs - 1])) <= 1e-10
 

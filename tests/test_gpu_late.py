@@ -11,6 +11,7 @@ import amg_amd as AMG
 from amg_amd.device import DeviceHierarchy
 from conftest import uniform
 from oracle import oracle as O
+from sweep_bound import assert_sweep_within_bound, directional
 from test_gpu_flow import _irregular_long_rows, rel, tunables
 
 pytestmark = pytest.mark.gpu
@@ -54,6 +55,11 @@ def test_split_row_sum_is_the_oracle_sweep_to_rounding(case):
         assert np.max(np.abs(x_late - xo)) <= 1e-13 * np.max(np.abs(xo)), (case, repr(pre))
         if not isinstance(pre, AMG.SOR):
             assert np.array_equal(x_in, xo)
+        # per row: within (m_i + 4) u of the exact update from the same inputs (tests/sweep_bound.py) — for the smoothers that make
+        # ONE directional pass; symmetric and repeated sweeps are two or more passes whose intermediate iterate is not observable
+        if directional(pre):
+            assert_sweep_within_bound(A, x0, bb, x_late, *directional(pre), what="LATE " + repr(pre))
+            assert_sweep_within_bound(A, x0, bb, x_in, *directional(pre), what="stored order " + repr(pre))
 
 
 def test_rows_too_unbalanced_for_the_split_keep_the_stored_order():
@@ -149,6 +155,18 @@ def test_float32_instance_split_row_sum():
     assert x_late.dtype == F32 and rel(x_late.astype(np.float64), x_in.astype(np.float64)) <= 1e-6
     zo = O.OracleHierarchy(ml, dtype=F32).precond(b)
     assert rel(z.astype(np.float64), zo.astype(np.float64)) <= F32_TOL
+    # one directional sweep at a time, row by row within the Float32 bound (tests/sweep_bound.py): LATE and stored order
+    for pre in (AMG.GaussSeidel(AMG.ForwardSweep()), AMG.GaussSeidel(AMG.BackwardSweep()), AMG.SOR(1.3, AMG.ForwardSweep()),
+                AMG.SOR(0.7, AMG.BackwardSweep())):
+        mlp = AMG.ruge_stuben(A, presmoother=pre, postsmoother=pre)
+        with tunables(lib, gs_bw=2, gs_bw_rows=128, gs_lean=0):
+            dev = DeviceHierarchy(mlp, 0, 1, dtype=F32)
+            x_in = dev.smooth(0, False, x0, b)
+            with tunables(lib, gs_bw_inorder=0):
+                assert lib.amgh_debug_bw_late(dev.h, 0) == 1
+                x_late = dev.smooth(0, False, x0, b)
+        assert_sweep_within_bound(A, x0, b, x_late, *directional(pre), dtype=F32, what="LATE f32 " + repr(pre))
+        assert_sweep_within_bound(A, x0, b, x_in, *directional(pre), dtype=F32, what="stored order f32 " + repr(pre))
 
 
 def test_split_row_sum_zero_diagonals_and_rows_that_must_divide():
@@ -189,3 +207,6 @@ def test_split_row_sum_zero_diagonals_and_rows_that_must_divide():
         assert np.max(np.abs(x_late[ok] - xo[ok]) / np.maximum(np.abs(xo[ok]), floor)) <= 1e-12, repr(pre)
         for r in (0, 777, 3000, n - 1):
             assert x_late[r] == x0[r]      # zero diagonal: untouched
+        if directional(pre):
+            assert_sweep_within_bound(A, x0, bb, x_late, *directional(pre), what="LATE " + repr(pre))
+            assert_sweep_within_bound(A, x0, bb, x_in, *directional(pre), what="stored order " + repr(pre))

@@ -10,6 +10,7 @@ import amg_amd as AMG
 from amg_amd.device import smooth_standalone
 from conftest import load_csc, load_npz, uniform
 from oracle import oracle as O
+from sweep_bound import assert_sweep_within_bound, directional
 
 pytestmark = pytest.mark.gpu
 
@@ -60,6 +61,8 @@ def test_quad_walk_sweeps_equal_the_scalar_loop(quad, sm):
     quad.amgh_debug_set_tunable(b"gs_wave_quad", 1)
     assert np.array_equal(x1, xo)
     assert not np.array_equal(x, x1) and rel(x, x1) <= TIGHT
+    if directional(smoother):   # per row: within (m_i + 4) u of the exact update from the same inputs (tests/sweep_bound.py)
+        assert_sweep_within_bound(A, x0, b, x, *directional(smoother), what="four lanes " + sm)
 
 
 def test_quad_walk_c5_cycles_and_cg(quad):
@@ -126,3 +129,5 @@ def test_quad_walk_zero_diagonals_and_rows_that_must_divide(quad):
         assert np.max(np.abs(x[ok] - xo[ok]) / np.maximum(np.abs(xo[ok]), floor)) <= 1e-12, repr(sm)
         for r in (0, 77, n - 1):
             assert x[r] == x0[r]
+        if directional(sm):
+            assert_sweep_within_bound(A, x0, b, x, *directional(sm), what="four lanes " + repr(sm))
