@@ -5,9 +5,13 @@ One "step" = one V-cycle of the hot path (`ldiv!` semantics of preconditioner.jl
 one `__solve!`, multilevel.jl:214-239) over the whole 16.7 M-unknown system, on the hierarchy
 built by `ruge_stuben` defaults (symmetric Gauss-Seidel pre/post), with b already resident in HBM.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--size 256] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--size 256] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...   (N > 1, a launcher's RANK / WORLD_SIZE)
     python bench.py --gpus N ...        (N > 1, no launcher: bench.py spawns its N ranks itself, `self_launch`)
+
+A plain run does what the headline figure needs: set up, warm up, time the steps, write --dump-outputs, print the line.
+--full also measures and checks the rest (roofline and per-kernel figures, time to solution, a block of right-hand sides,
+the uncompressed layouts, the smaller configurations, the CPU baseline and the parity against the oracle: full_measurements).
 
 Prints ONE JSON line (rank 0).  See DESIGN.md §Measurement for the definitions.
 """
@@ -355,13 +359,16 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--size", type=int, default=256, help="grid points per axis (256 = the headline config)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline figure, also measure and check everything else the line can report (full_measurements; "
+                         "N > 1: the secondary configurations and the CPU baseline); the --no-* options below and --light trim it")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and the parity check against the oracle")
     ap.add_argument("--cpu-budget", type=float, default=20.0)
-    ap.add_argument("--light", action="store_true", help="profiling runs: skip the extra smoother timing")
-    ap.add_argument("--no-block-rhs", action="store_true", help="skip the secondary measurement on a block of 8 right-hand sides")
-    ap.add_argument("--no-uncompressed", action="store_true", help="skip the secondary cycle on the uncompressed layouts (a second layout of the hierarchy: ~6 s, ~24 GB)")
-    ap.add_argument("--no-secondary-configs", action="store_true", help="skip the C1 / C2 / C5 cycles")
-    ap.add_argument("--no-pmc", action="store_true", help="skip the two rocprofv3 --pmc passes behind roofline.traffic")
+    ap.add_argument("--light", action="store_true", help="with --full: profiling runs: skip the extra smoother timing")
+    ap.add_argument("--no-block-rhs", action="store_true", help="with --full: skip the secondary measurement on a block of 8 right-hand sides")
+    ap.add_argument("--no-uncompressed", action="store_true", help="with --full: skip the secondary cycle on the uncompressed layouts (a second layout of the hierarchy: ~6 s, ~24 GB)")
+    ap.add_argument("--no-secondary-configs", action="store_true", help="with --full: skip the C1 / C2 / C5 cycles")
+    ap.add_argument("--no-pmc", action="store_true", help="with --full: skip the two rocprofv3 --pmc passes behind roofline.traffic")
     ap.add_argument("--force-dist", action="store_true", help="run the row-sharded driver even with one rank")
     ap.add_argument("--transport", default=None, choices=("rccl", "ipc", "ipc-staged"),
                     help="N > 1: halo transport of the primary measurement (default: AMGH_DIST_TRANSPORT or rccl)")
@@ -369,7 +376,7 @@ def main():
                     help="N > 1: smoother of the primary measurement (gs = ruge_stuben defaults; jacobi = Jacobi(2/3))")
     ap.add_argument("--no-preflight", action="store_true", help="N > 1: skip the 32^3 two-cycle exchange that tries every transport before the timed problem")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="N > 1: skip the secondary measurements (Jacobi-smoothed hierarchy, IPC transport)")
+                    help="N > 1, with --full: skip the secondary measurements (Jacobi-smoothed hierarchy, IPC transport)")
     ap.add_argument("--setup", default="gpu", choices=("gpu", "host"), help="where the data-parallel half of ruge_stuben runs")
     ap.add_argument("--host-exec", action="store_true",
                     help="N > 1 launcher self-test on a box without GPUs: the library's own sharded cycle (amgh_dist_*) executed in host "
@@ -386,6 +393,9 @@ def main():
     if args.gpus > 1 and "RANK" not in os.environ and "WORLD_SIZE" not in os.environ:
         return self_launch(args.gpus)   # started the way `--gpus 1` is started: no launcher — be the launcher
     if args.gpus > 1 or args.force_dist or args.host_exec:
+        if not args.full:
+            # a plain run: the primary configuration alone, with its preflight (which picks the transport) and its parity check
+            args.no_secondary = args.no_cpu_baseline = True
         from bench_dist import main_distributed  # row-sharded path (torch.distributed over RCCL)
         return main_distributed(args)
 
@@ -436,7 +446,7 @@ def main():
         if rc != 0:
             raise SystemExit("bench.py: amgh_dev_sync: " + lib.amgh_strerror(rc).decode())
 
-    clocks_before = smi_state()
+    clocks_before = smi_state() if args.full else None
     for _ in range(args.warmup):
         step()
     sync()
@@ -445,12 +455,56 @@ def main():
         step()
     sync()
     elapsed = time.perf_counter() - t0
-    clocks_after = smi_state()
+    clocks_after = smi_state() if args.full else None
     ms_per_step = 1e3 * elapsed / args.steps
     value = n * args.steps / elapsed
-    z_timed = zd.download()      # what the LAST timed V-cycle produced (checked against the oracle below)
+    z_timed = zd.download()      # what the LAST timed V-cycle produced (checked against the oracle with --full)
     if args.dump_outputs:
         dump_outputs(args.dump_outputs, z_timed)
+
+    vb = vcycle_bytes(ml, 4)
+    out = {
+        "metric": f"V-cycle unknowns/sec + fine-level SpMV GB/s (% HBM peak), 3-D Poisson {N}^3",
+        "value": value, "unit": "unknowns/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
+        "dtype": "f64", "data": "synthetic",
+        "config": {"workload": "poisson((%d,%d,%d)) 7-point, ruge_stuben defaults (theta=0.25, symmetric "
+                               "Gauss-Seidel pre+post), one V-cycle per step (ldiv!), b ~ U[0,1) splitmix64 seed 0"
+                               % (N, N, N),
+                   "unknowns": n, "nnz": A.nnz, "levels": len(ml),
+                   "level_sizes": [l.A.m for l in ml.levels] + [ml.final_A.m],
+                   "operator_complexity": round(AMG.operator_complexity(ml), 3),
+                   "gs_dependency_levels": [dev.gs_dependency_levels(l) for l in range(len(ml.levels))],
+                   "gs_sweep_steps_fwd_bwd": [[dev.gs_sweep_steps(l, False), dev.gs_sweep_steps(l, True)]
+                                              for l in range(len(ml.levels))],
+                   "parallelism": "1 GPU"},
+        # (EFFECTIVE figures: the 12-bytes-per-entry count of BASELINE.md section 4 over the measured time — with the dictionary
+        # records and the value-coded columns the kernels MOVE fewer bytes than this count, sweep_roofline.bytes_streamed_per_cycle)
+        "vcycle": {"algorithmic_bytes": vb, "achieved_GBs": vb / (ms_per_step * 1e-3) / 1e9,
+                   "frac_of_hbm_peak": vb / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                   "frac_of_hbm_peak_is": "effective (algorithmic 12-byte count / time), not bytes moved / time",
+                   "fine_symmetric_gs_ms": None},
+        "setup_s": t_setup, "setup_s_parts": {"poisson_generation_s": t_problem, "ruge_stuben_s": t_setup - t_problem,
+                                               "note": "setup_s = the seconds before the first cycle, the generation of the operator included; "
+                                                       "ruge_stuben_s is what the reference's ruge_stuben(A) call corresponds to"},
+        "upload_s": t_upload, "setup_overlapped_with_upload": bool(overlap),
+        **({"overlap_error": overlap_error} if overlap_error else {}),
+        "hbm_bytes": dev.device_bytes(), "hbm_bytes_by_category": dev.device_bytes_detail(),
+        "collapsed_tail": tail_info(dev),
+    }
+    if args.full:
+        full_measurements(args, out, A, ml, dev, b, bd, zd, z_timed, step, sync, (clocks_before, clocks_after))
+    print(json.dumps(out))
+
+
+def full_measurements(args, out, A, ml, dev, b, bd, zd, z_timed, step, sync, clocks):
+    """--full: what the line reports beyond its headline figure, measured after the timed steps in runs of their own (the
+    per-kernel and roofline figures, time to solution, a block of right-hand sides, the uncompressed layouts, the smaller
+    configurations, the CPU baseline) and the parity of the last timed V-cycle against the oracle.  Adds to `out`."""
+    import amg_amd as AMG
+    N, n, lib = args.size, A.m, dev.lib
+    ms_per_step = out["ms_per_step"]
+    clocks_before, clocks_after = clocks
 
     # dominant kernel of the metric: the fine-level CSR SpMV, timed with HIP events on its own stream
     spmv_ms = dev.bench_op(0, 0, reps=50, warmup=5)
@@ -506,23 +560,9 @@ def main():
         smooth_ms = float(sum(prof[k].sum() for k in prof if k in ("Presmoother", "Postsmoother"))) / 3.0
         cycle_breakdown = {k: round(float(prof[k].sum()) / 3.0, 4) for k in prof}
 
-    vb = vcycle_bytes(ml, 4)
     traffic, traffic_how = pmc_traffic(N, enabled=not args.no_pmc and not args.light)
-    out = {
-        "metric": f"V-cycle unknowns/sec + fine-level SpMV GB/s (% HBM peak), 3-D Poisson {N}^3",
-        "value": value, "unit": "unknowns/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
-        "dtype": "f64", "data": "synthetic",
-        "config": {"workload": "poisson((%d,%d,%d)) 7-point, ruge_stuben defaults (theta=0.25, symmetric "
-                               "Gauss-Seidel pre+post), one V-cycle per step (ldiv!), b ~ U[0,1) splitmix64 seed 0"
-                               % (N, N, N),
-                   "unknowns": n, "nnz": A.nnz, "levels": len(ml),
-                   "level_sizes": [l.A.m for l in ml.levels] + [ml.final_A.m],
-                   "operator_complexity": round(AMG.operator_complexity(ml), 3),
-                   "gs_dependency_levels": [dev.gs_dependency_levels(l) for l in range(len(ml.levels))],
-                   "gs_sweep_steps_fwd_bwd": [[dev.gs_sweep_steps(l, False), dev.gs_sweep_steps(l, True)]
-                                              for l in range(len(ml.levels))],
-                   "parallelism": "1 GPU"},
+    out["vcycle"]["fine_symmetric_gs_ms"] = sweep_ms
+    out.update({
         "roofline": {"bound": "hbm", "kernel": "csr_stream_kernel<SPMV, StreamCfg<1024,1024,8192,4>> (fine-level A, %d rows, %d nnz)" % (n, A.nnz),
                      "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
                      "traffic": traffic, "traffic_source": traffic_how, "algorithmic_bytes": alg, "avg_launch_ms": spmv_ms,
@@ -533,12 +573,6 @@ def main():
                      "gpu_state_before_timed_region": clocks_before, "gpu_state_after_timed_region": clocks_after,
                      "fused_residual_ms": resid_ms,
                      "fused_residual_GBs": (alg + 8 * n) / (resid_ms * 1e-3) / 1e9},
-        # (EFFECTIVE figures: the 12-bytes-per-entry count of BASELINE.md section 4 over the measured time — with the dictionary
-        # records and the value-coded columns the kernels MOVE fewer bytes than this count, sweep_roofline.bytes_streamed_per_cycle)
-        "vcycle": {"algorithmic_bytes": vb, "achieved_GBs": vb / (ms_per_step * 1e-3) / 1e9,
-                   "frac_of_hbm_peak": vb / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                   "frac_of_hbm_peak_is": "effective (algorithmic 12-byte count / time), not bytes moved / time",
-                   "fine_symmetric_gs_ms": sweep_ms},
         # second roofline entry: the kernels that dominate the CYCLE (Gauss-Seidel sweeps: gs_slot / gs_bigslot /
         # chain / block launches + pre-pass), latency-bound — one launch per merged group of dependency levels
         "sweep_roofline": {
@@ -564,14 +598,7 @@ def main():
             "peak": HBM_PEAK_GBS, "unit": "GB/s",
             "frac": None if smooth_ms is None else alg_sweeps / (smooth_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
             "per_level": [{"fwd": p["fwd"], "bwd": p["bwd"]} for p in sweeps[:6]]},
-        "setup_s": t_setup, "setup_s_parts": {"poisson_generation_s": t_problem, "ruge_stuben_s": t_setup - t_problem,
-                                               "note": "setup_s = the seconds before the first cycle, the generation of the operator included; "
-                                                       "ruge_stuben_s is what the reference's ruge_stuben(A) call corresponds to"},
-        "upload_s": t_upload, "setup_overlapped_with_upload": bool(overlap),
-        **({"overlap_error": overlap_error} if overlap_error else {}),
-        "hbm_bytes": dev.device_bytes(), "hbm_bytes_by_category": dev.device_bytes_detail(),
-        "collapsed_tail": tail_info(dev),
-    }
+    })
     if not args.light:
         # secondary (never `value`): time to SOLUTION on the same hierarchy — the device-resident preconditioned CG of amgh_pcg_d
         # (cg(A, b; Pl = aspreconditioner(ml)) as the reference's tests run it, cycle_tests.jl:25), right-hand side and solution in
@@ -595,7 +622,7 @@ def main():
             As = A.to_scipy()
             true_res = float(np.linalg.norm(b - As @ xs) / np.linalg.norm(b))
             out["pcg_to_solution"] = {"reltol": rtol, "iterations": int(its.value), "ms": t_pcg, "ms_per_iteration": t_pcg / max(1, its.value),
-                                      "true_rel_residual": true_res, "setup_plus_solve_s": t_setup + 1e-3 * t_pcg,
+                                      "true_rel_residual": true_res, "setup_plus_solve_s": out["setup_s"] + 1e-3 * t_pcg,
                                       "what": "amgh_pcg_d: V-cycle-preconditioned CG, b and x resident in HBM (IterativeSolvers.cg semantics)"}
             del xd, As, xs
         except Exception as ex:  # noqa: BLE001
@@ -657,7 +684,6 @@ def main():
         out["parity"] = {"rel_err_vs_oracle": err, "tolerance": 1e-10, "what": "||z - z_oracle|| / ||z_oracle|| of the last timed V-cycle"}
         if not err <= 1e-10:
             raise SystemExit(f"bench.py: the timed V-cycle differs from the oracle: rel.err {err:.3e} > 1e-10")
-    print(json.dumps(out))
 
 
 if __name__ == "__main__":

@@ -126,6 +126,17 @@ def test_bench_gpus_2_starts_by_itself_and_finishes():
     assert time.perf_counter() - t0 < 300
 
 
+def test_bench_full_host_exec_reports_cpu_baseline():
+    """`--full` at N > 1: rank 0 also times the CPU restatement of the reference's cycle (a plain run leaves it out)."""
+    import json
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--size", "16", "--steps", "1", "--warmup", "0",
+                        "--host-exec", "--full", "--cpu-budget", "0.5"], env=_clean_env(), stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600, cwd=ROOT)
+    assert r.returncode == 0, r.stderr.decode()[-3000:]
+    d = json.loads(r.stdout.decode().strip())
+    assert d["n_gpus"] == 2 and d["parity"]["ok"]
+    assert d["cpu_baseline"]["value"] > 0 and d["cpu_baseline"]["kind"] == "port"
+
+
 def test_bench_gpus_3_host_exec_three_ranks():
     import json
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "3", "--size", "20", "--steps", "1", "--warmup", "0",

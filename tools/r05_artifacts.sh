@@ -3,8 +3,8 @@
 mkdir -p gpurun_out/r5/final
 R=$PWD
 O=$R/gpurun_out/r5/final
-timeout 700 python bench.py > $O/bench_256.json 2> $O/bench_256.err
-(cd /tmp && export TMPDIR=/tmp && rm -rf /tmp/rp_r05 && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/rp_r05 -- python $R/bench.py --steps 1 --warmup 0 --no-cpu-baseline --light > $O/rocprof_run.log 2>&1; f=$(find /tmp/rp_r05 -name "*kernel_trace.csv" | head -1); python $R/tools/rocprof_summary.py $f $O/rocprofv3_kernel_stats_bench256.txt > /dev/null 2>&1)
+timeout 700 python bench.py --full > $O/bench_256.json 2> $O/bench_256.err
+(D=$(mktemp -d) && cd $D && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $D/rp -- python $R/bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --light > $O/rocprof_run.log 2>&1; f=$(find $D/rp -name "*kernel_trace.csv" | head -1); python $R/tools/rocprof_summary.py $f $O/rocprofv3_kernel_stats_bench256.txt > /dev/null 2>&1; rm -rf $D)
 timeout 600 python tools/vcycle_profile.py 256 3 > $O/vcycle_profile.log 2>&1
 ls -la $O
 python -c "

@@ -9,7 +9,7 @@ for r in rows:
     agg[r["Kernel_Name"]].append((int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3)
 tot = sum(sum(v) for v in agg.values())
 with open(out, "w") as f:
-    f.write("command: rocprofv3 --kernel-trace --stats --output-format csv -- python bench.py --steps 1 --warmup 0 --no-cpu-baseline --light   (MI355X, 256^3)\n")
+    f.write("command: rocprofv3 --kernel-trace --stats --output-format csv -- python bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --light   (MI355X, 256^3)\n")
     f.write("%-118s %7s %12s %10s %9s %10s %6s\n" % ("kernel", "calls", "total_us", "avg_us", "min_us", "max_us", "%"))
     for k, v in sorted(agg.items(), key=lambda kv: -sum(kv[1])):
         f.write("%-118s %7d %12.1f %10.2f %9.2f %10.2f %6.1f\n" % (k[:118], len(v), sum(v), sum(v) / len(v), min(v), max(v), 100 * sum(v) / tot))
