@@ -10,6 +10,7 @@ The directory name contains a dot, so import it through the repo-root alias:
     ml = AMG.ruge_stuben(A)
     x  = AMG._solve(ml, A @ np.ones(A.m))
     p  = AMG.aspreconditioner(ml); x = AMG.cg(A, b, Pl=p)
+    X  = AMG.cg(A, B, Pl=p)      # B: n x bs, an independent cg per column on the block cycle
     x  = AMG.gmres(M, b, Pl=AMG.aspreconditioner(AMG.ruge_stuben(M, symmetry=AMG.NoSymmetry())))
 """
 from ._libs import AMGError, gpu_available, hip_lib, setup_lib  # noqa: F401

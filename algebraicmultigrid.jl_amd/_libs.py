@@ -142,6 +142,9 @@ def _bind_solve_phase(L, creal, coarse_fn):
     L.amgh_gmres.argtypes = gmres_args
     L.amgh_gmres_d.argtypes = gmres_args
     L.amgh_debug_gmres_reorth.argtypes = [vp]
+    pcg_block_args = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, vp, C.c_int, vp]
+    L.amgh_pcg_block.argtypes = pcg_block_args
+    L.amgh_pcg_block_d.argtypes = pcg_block_args
     L.amgh_level_spmv.argtypes = [vp, C.c_int, C.c_int, vp, vp]
     L.amgh_level_spmv_d.argtypes = [vp, C.c_int, C.c_int, vp, vp]
     L.amgh_level_residual_d.argtypes = [vp, C.c_int, vp, vp, vp]

@@ -15,6 +15,7 @@
 #include "gs_schedule.hpp"
 #include "csr_ops.hpp"
 #include "gmres_kernels.hpp"
+#include "pcg_block_kernels.hpp"
 
 namespace {
 
@@ -77,6 +78,10 @@ struct amgh_handle {
   int* gm_flags = nullptr;
   int64_t gm_ld = 0;
   int gm_cols = 0, gm_reorth = -1;
+  // PCG on the block (allocated by the first amgh_pcg_block): r, c, u (n x nrhs each), nrhs x kRedBlocks dot partials, the
+  // per-column scalars and the status record (pcg_block_kernels.hpp)
+  real *pb_r = nullptr, *pb_c = nullptr, *pb_u = nullptr, *pb_part = nullptr, *pb_sc = nullptr;
+  PbStatus* pb_st = nullptr;
   int64_t ws_bytes = 0;
   // profiling
   bool profile = false;
@@ -748,6 +753,83 @@ int gmres_dev(amgh_t* h, const real* b, real* x, int cyc, int use_precond, int r
   return bw_err_check();
 }
 
+// nrhs independent cg's on the handle's block (pcg_block_kernels.hpp): column j is pcg_dev's recurrence on B[:, j], x0 = 0,
+// with its own tol_j = max(reltol |b_j|, abstol); it freezes when !(|r_j| > tol_j) or after maxiter iterations, and the call
+// returns when no column is active.  A fixed launch plan per iteration, one status copy and one synchronisation.
+int pcg_block_blocks(int64_t n, int w) {
+  return (int)std::max<int64_t>(1, std::min<int64_t>(kRedBlocks, (n / w + kThreads - 1) / kThreads));
+}
+
+template <int W>
+int pcg_block_launch(amgh_t* h, int what, real* x, bool xv, int64_t n, int nb) {
+  const int bs = h->nrhs;
+  const PbStatus* st = h->pb_st;
+  switch (what) {
+    case 0: hipLaunchKernelGGL(pcg_block_dots_kernel<W>, dim3(nb), dim3(kThreads), 0, h->stream, (const real*)h->pb_r, (const real*)h->pb_r, n, bs, st, 1, h->pb_part); break;
+    case 1: hipLaunchKernelGGL(pcg_block_dots_kernel<W>, dim3(nb), dim3(kThreads), 0, h->stream, (const real*)h->pb_c, (const real*)h->pb_r, n, bs, st, 0, h->pb_part); break;
+    case 2: hipLaunchKernelGGL(pcg_block_xpby_kernel<W>, dim3(nb), dim3(kThreads), 0, h->stream, h->pb_u, (const real*)h->pb_c, n, bs, (const real*)h->pb_sc, st); break;
+    case 3: hipLaunchKernelGGL(pcg_block_dots_kernel<W>, dim3(nb), dim3(kThreads), 0, h->stream, (const real*)h->pb_u, (const real*)h->pb_c, n, bs, st, 0, h->pb_part); break;
+    case 4:
+      if (xv) hipLaunchKernelGGL((pcg_block_update_kernel<W, true>), dim3(nb), dim3(kThreads), 0, h->stream, x, (const real*)h->pb_u, h->pb_r, h->pb_c, n, bs, (const real*)h->pb_sc, st, h->pb_part);
+      else hipLaunchKernelGGL((pcg_block_update_kernel<W, false>), dim3(nb), dim3(kThreads), 0, h->stream, x, (const real*)h->pb_u, h->pb_r, h->pb_c, n, bs, (const real*)h->pb_sc, st, h->pb_part);
+      break;
+  }
+  HIP_TRY(hipGetLastError());
+  return AMGH_OK;
+}
+
+int pcg_block_dev(amgh_t* h, const real* B, real* X, int cyc, int use_precond, int maxiter, double abstol, double reltol,
+                  real* hist, int ldh, int* iters) {
+  const int64_t n = fine_n(h);
+  const int bs = h->nrhs;
+  const int64_t nn = n * bs;
+  // 16-byte vectors when every column starts on a 16-byte boundary (the workspace's do when n is a multiple of the width)
+  const bool vec = n % kGmVW == 0;
+  const bool xv = vec && reinterpret_cast<uintptr_t>(X) % 16 == 0;
+  const int nb = pcg_block_blocks(n, vec ? kGmVW : 1);
+  auto launch = [&](int what) { return vec ? pcg_block_launch<kGmVW>(h, what, X, xv, n, nb) : pcg_block_launch<1>(h, what, X, false, n, nb); };
+  auto scal = [&](int which) {
+    hipLaunchKernelGGL(pcg_block_scal_kernel, dim3(1), dim3(kPbScalThreads), 0, h->stream, (const real*)h->pb_part, nb, bs, h->pb_sc,
+                       h->pb_st, which, maxiter, abstol, reltol);
+    HIP_TRY(hipGetLastError());
+    return AMGH_OK;
+  };
+  RC_TRY(vec_fill(h, X, nn, 0.0));
+  RC_TRY(vec_fill(h, h->pb_u, nn, 0.0));
+  RC_TRY(vec_fill(h, h->pb_c, nn, 0.0));
+  RC_TRY(vec_copy(h, h->pb_r, B, nn));
+  RC_TRY(launch(0));   // |b_j|^2
+  RC_TRY(scal(3));
+  PbStatus st;
+  HIP_TRY(hipMemcpyAsync(&st, h->pb_st, sizeof(PbStatus), hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  if (hist)
+    for (int j = 0; j < bs; ++j) hist[(int64_t)j * ldh] = st.res[j];
+  int done[kPbMaxCols] = {0};
+  while (st.nactive > 0) {
+    if (use_precond) RC_TRY(apply_cycle(h, h->pb_c, h->pb_r, cyc, true));
+    else RC_TRY(vec_copy(h, h->pb_c, h->pb_r, nn));
+    RC_TRY(launch(1));   // c.r
+    RC_TRY(scal(0));
+    RC_TRY(launch(2));   // u = c + beta u
+    RC_TRY(csr_apply(h->levels.empty() ? &h->finalA : &h->levels[0]->A, M_SPMV, h->pb_u, nullptr, h->pb_c, h->stream, bs));
+    RC_TRY(launch(3));   // u.c
+    RC_TRY(scal(1));
+    RC_TRY(launch(4));   // x, r, |r|^2
+    RC_TRY(scal(2));
+    HIP_TRY(hipMemcpyAsync(&st, h->pb_st, sizeof(PbStatus), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    for (int j = 0; j < bs; ++j) {
+      if (st.iters[j] == done[j]) continue;
+      done[j] = st.iters[j];
+      if (hist && done[j] < ldh) hist[(int64_t)j * ldh + done[j]] = st.res[j];
+    }
+  }
+  for (int j = 0; j < bs; ++j) iters[j] = st.iters[j];
+  RC_TRY(prof_flush(h));
+  return bw_err_check();
+}
+
 int check_ready(const amgh_t* h) {
   if (!h) return AMGH_EINVAL;
   if (!h->finalized) return AMGH_ESTATE;
@@ -835,6 +917,7 @@ void amgh_destroy(amgh_t* h) {
   hipFree(h->coarse_op); hipFree(h->res_final); hipFree(h->partial); hipFree(h->scal);
   hipFree(h->x0); hipFree(h->b0); hipFree(h->pc_r); hipFree(h->pc_c); hipFree(h->pc_u);
   hipFree(h->gm_V); hipFree(h->gm_t); hipFree(h->gm_sc); hipFree(h->gm_part); hipFree(h->gm_flags);
+  hipFree(h->pb_r); hipFree(h->pb_c); hipFree(h->pb_u); hipFree(h->pb_part); hipFree(h->pb_sc); hipFree(h->pb_st);
   for (auto& t : h->tail) hipFree(t.M);
   for (auto& e : h->pending) { hipEventDestroy(e.a); hipEventDestroy(e.b); }
   for (auto& g : h->graphs) if (g.exec) hipGraphExecDestroy(g.exec);
@@ -1647,6 +1730,40 @@ int amgh_gmres(amgh_t* h, const real* b, real* x, int cycle_, int use_precond, i
 }
 
 int amgh_debug_gmres_reorth(const amgh_t* h) { return h ? h->gm_reorth : -1; }
+
+static int ensure_pcg_block_bufs(amgh_t* h) {
+  if (h->pb_st) return AMGH_OK;
+  const int64_t nn = fine_n(h) * h->nrhs;
+  if (!h->pb_r) RC_TRY(dev_alloc(&h->pb_r, nn));
+  if (!h->pb_c) RC_TRY(dev_alloc(&h->pb_c, nn));
+  if (!h->pb_u) RC_TRY(dev_alloc(&h->pb_u, nn));
+  if (!h->pb_part) RC_TRY(dev_alloc(&h->pb_part, (int64_t)h->nrhs * kRedBlocks));
+  if (!h->pb_sc) RC_TRY(dev_alloc(&h->pb_sc, (int64_t)kPbScal * kPbMaxCols));
+  RC_TRY(dev_alloc(&h->pb_st, 1));
+  h->ws_bytes += kRealB * (3 * nn + (int64_t)h->nrhs * kRedBlocks + kPbScal * kPbMaxCols) + (int64_t)sizeof(PbStatus);
+  return AMGH_OK;
+}
+
+int amgh_pcg_block_d(amgh_t* h, const real* B_d, real* X_d, int cycle_, int use_precond, int maxiter, double abstol,
+                     double reltol, real* resid_hist, int ldh, int* iters) {
+  RC_TRY(check_ready(h));
+  if (!B_d || !X_d || !iters || cycle_ < 0 || cycle_ > 2 || maxiter < 0 || (resid_hist && ldh < 1)) return AMGH_EINVAL;
+  HIP_TRY(hipSetDevice(h->device));
+  RC_TRY(ensure_pcg_block_bufs(h));
+  return pcg_block_dev(h, B_d, X_d, cycle_, use_precond, maxiter, abstol, reltol, resid_hist, ldh, iters);
+}
+
+int amgh_pcg_block(amgh_t* h, const real* B, real* X, int cycle_, int use_precond, int maxiter, double abstol,
+                   double reltol, real* resid_hist, int ldh, int* iters) {
+  RC_TRY(check_ready(h));
+  if (!B || !X) return AMGH_EINVAL;
+  HIP_TRY(hipSetDevice(h->device));
+  const int64_t nn = fine_n(h) * h->nrhs;
+  HIP_TRY(hipMemcpyAsync(h->b0, B, sizeof(real) * nn, hipMemcpyHostToDevice, h->stream));
+  RC_TRY(amgh_pcg_block_d(h, h->b0, h->x0, cycle_, use_precond, maxiter, abstol, reltol, resid_hist, ldh, iters));
+  HIP_TRY(hipMemcpy(X, h->x0, sizeof(real) * nn, hipMemcpyDeviceToHost));
+  return AMGH_OK;
+}
 
 static amgh_csr* level_op(amgh_t* h, int level, int which) {
   const int L = (int)h->levels.size();

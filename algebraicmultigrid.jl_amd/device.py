@@ -14,6 +14,7 @@ from .sparse import SparseMatrixCSC
 
 OP_A, OP_P, OP_R = 0, 1, 2
 CYCLE_V, CYCLE_W, CYCLE_F = 0, 1, 2
+PCG_BLOCK_HIST = 10000   # residual history rows kept per column by default (pcg_block): (n + 1) x bs reals would not fit
 T_LABELS = ["Presmoother", "Residual eval", "Restriction", "Coarse solve", "Prolongation", "Postsmoother"]
 
 
@@ -337,6 +338,28 @@ class DeviceHierarchy:
         hip_check(self.lib.amgh_pcg(self.h, b.ctypes.data, x.ctypes.data, cycle, int(bool(use_precond)), maxiter,
                                     abstol, reltol, hist.ctypes.data, C.byref(iters)), "pcg")
         return x, hist[:iters.value + 1].copy(), iters.value
+
+    def pcg_block(self, B, cycle=CYCLE_V, use_precond=True, maxiter=None, abstol=0.0, reltol=None, ldh=None):
+        """nrhs independent cg's on the device (amgh_pcg_block): column j is IterativeSolvers.jl's cg on B[:, j] with
+        x0 = 0 and its own tolerance max(reltol * |b_j|, abstol).  B: n x nrhs (the handle's block size).  maxiter
+        defaults to n, reltol to sqrt(eps), ldh (history rows kept per column) to min(maxiter, PCG_BLOCK_HIST) + 1.
+        Returns (X, hists, iters): X n x nrhs in Fortran order, hists[j] = |r_j| after 0, 1, ... iterations (at most ldh
+        entries), iters an int array."""
+        B = np.asfortranarray(B, dtype=self.dtype)
+        if B.ndim == 1:
+            B = B.reshape(-1, 1, order="F")
+        if B.shape != (self.n, self.nrhs):
+            raise AMGError("pcg_block: B must be %d x %d, got %s" % (self.n, self.nrhs, B.shape))
+        maxiter = self.n if maxiter is None else int(maxiter)
+        reltol = float(np.sqrt(np.finfo(self.dtype).eps)) if reltol is None else float(reltol)
+        ldh = min(max(maxiter, 0), PCG_BLOCK_HIST) + 1 if ldh is None else int(ldh)
+        X = np.zeros_like(B, order="F")
+        H = np.zeros((max(ldh, 1), self.nrhs), dtype=self.dtype, order="F")
+        iters = np.zeros(self.nrhs, dtype=np.intc)
+        hip_check(self.lib.amgh_pcg_block(self.h, B.ctypes.data, X.ctypes.data, cycle, int(bool(use_precond)), maxiter,
+                                          float(abstol), reltol, H.ctypes.data, ldh, iters.ctypes.data), "pcg_block")
+        hists = [H[:min(int(k), ldh - 1) + 1, j].copy() for j, k in enumerate(iters)]
+        return X, hists, iters.astype(np.int64)
 
     def gmres(self, b, cycle=CYCLE_V, use_precond=True, restart=None, maxiter=None, abstol=0.0, reltol=None):
         """Restarted, left-preconditioned GMRES on the device (amgh_gmres): IterativeSolvers.jl's gmres with x0 = 0.

@@ -221,10 +221,16 @@ def aspreconditioner(ml, cycle=None):
     return Preconditioner(ml, cycle)
 
 
-def cg(A, b, Pl=None, abstol=0.0, reltol=_SQRT_EPS, maxiter=None, log=False):
+def cg(A, b, Pl=None, abstol=0.0, reltol=None, maxiter=None, log=False):
     """IterativeSolvers.jl `cg(A, b; Pl, abstol, reltol, maxiter, log)` as the reference's tests use it
     (cycle_tests.jl:25, runtests.jl:186,204).  Runs entirely on device (amgh_pcg); A must be the
-    fine-level operator of Pl's hierarchy."""
+    fine-level operator of Pl's hierarchy.  reltol defaults to sqrt(eps(Float64)).
+
+    b may also be an n x bs matrix (1 <= bs <= 64): then every column is its own cg (`cg(A, b[:, j])`, not block CG),
+    all of them on the hierarchy's n x bs block in one device-resident call (amgh_pcg_block), in the arithmetic type
+    _arith_dtype picks (a Float32 hierarchy with a Float32 block runs the Float32 instance; reltol then defaults to
+    sqrt(eps(Float32))).  Column j stops at |r_j| <= max(reltol * |b_j|, abstol).  With log the info holds per-column
+    values: "iters" (int array), "resnorm" (list of arrays; at most PCG_BLOCK_HIST entries each) and "isconverged"."""
     if not isinstance(Pl, Preconditioner):
         raise AMGError("cg: Pl must be aspreconditioner(ml)")
     ml = Pl.ml
@@ -233,12 +239,39 @@ def cg(A, b, Pl=None, abstol=0.0, reltol=_SQRT_EPS, maxiter=None, log=False):
     if A is not fine and not (A.shape == fine.shape and A.nnz == fine.nnz and np.array_equal(A.colptr, fine.colptr)
                               and np.array_equal(A.rowval, fine.rowval) and np.array_equal(A.nzval, fine.nzval)):
         raise AMGError("cg: A must be the operator the preconditioner was built from")
+    if np.ndim(b) == 2:
+        return _cg_block(A, b, Pl, abstol, reltol, maxiter, log)
+    reltol = _SQRT_EPS if reltol is None else reltol
     b = np.asarray(b, dtype=np.float64)
     maxiter = A.n if maxiter is None else int(maxiter)
     x, hist, iters = ml.device().pcg(b, _cycle_code(Pl.cycle), True, maxiter, float(abstol), float(reltol))
     if log:
         return x, {"iters": iters, "resnorm": hist[1:], "isconverged": bool(hist[-1] <= max(reltol * hist[0], abstol))}
     return x
+
+
+def _cg_block(A, B, Pl, abstol, reltol, maxiter, log):
+    """cg on each column of an n x bs block (see cg)."""
+    ml = Pl.ml
+    dt = _arith_dtype(ml, B)
+    B = np.asfortranarray(B, dtype=dt)
+    bs = B.shape[1]
+    if not 1 <= bs <= 64:
+        raise AMGError("cg: a block of right-hand sides has 1 to 64 columns, got %d" % bs)
+    if B.shape[0] != A.n:
+        raise AMGError("cg: b has %d rows, A is %d x %d" % (B.shape[0], A.m, A.n))
+    reltol = float(np.sqrt(np.finfo(dt).eps)) if reltol is None else float(reltol)
+    maxiter = A.n if maxiter is None else int(maxiter)
+    X, hists, iters = ml.device(nrhs=bs, dtype=dt).pcg_block(B, _cycle_code(Pl.cycle), True, maxiter, float(abstol), reltol)
+    if not log:
+        return X
+    conv = np.zeros(bs, dtype=bool)
+    for j, h in enumerate(hists):
+        if len(h) == iters[j] + 1:
+            conv[j] = bool(h[-1] <= max(reltol * h[0], abstol))
+        else:   # (history cut at PCG_BLOCK_HIST entries: a column that stopped before maxiter met its tolerance)
+            conv[j] = bool(iters[j] < maxiter)
+    return X, {"iters": iters, "resnorm": [h[1:] for h in hists], "isconverged": conv}
 
 
 def gmres(A, b, Pl=None, restart=None, abstol=0.0, reltol=None, maxiter=None, log=False):

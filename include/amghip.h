@@ -256,6 +256,17 @@ int amgh_gmres_d(amgh_t* h, const amgh_real* b_d, amgh_real* x_d, int cycle, int
 /* Diagnostics: DGKS re-orthogonalisation passes the handle's last amgh_gmres(_d) call ran (-1: none yet). */
 int amgh_debug_gmres_reorth(const amgh_t* h);
 
+/* nrhs independent cg's on the handle's block (B, X: n x nrhs, column-major), x0 = 0, each column exactly
+ * IterativeSolvers.jl's cg(A, B[:, j]; Pl = aspreconditioner(ml), abstol, reltol, maxiter) — not block CG: the columns
+ * share no Krylov space.  Column j stops when !(|r_j| > max(reltol*|b_j|, abstol)) or after maxiter iterations and is
+ * frozen from then on; the call returns when no column is active.  Any nrhs in [1, 64]; the workspace (3 n nrhs reals)
+ * is allocated at the first call.  resid_hist: NULL, or ldh x nrhs column-major — column j's |r| after k iterations at
+ * [j*ldh + k] for k <= min(iters[j], ldh - 1).  iters: nrhs ints.                                                    */
+int amgh_pcg_block(amgh_t* h, const amgh_real* B, amgh_real* X, int cycle, int use_precond, int maxiter,
+                   double abstol, double reltol, amgh_real* resid_hist, int ldh, int* iters);
+int amgh_pcg_block_d(amgh_t* h, const amgh_real* B_d, amgh_real* X_d, int cycle, int use_precond, int maxiter,
+                     double abstol, double reltol, amgh_real* resid_hist, int ldh, int* iters);
+
 /* ------------------------------------------------------------------------- */
 /* Per-level operators — unit-test and roofline hooks                           */
 /* ------------------------------------------------------------------------- */

@@ -188,6 +188,21 @@ function cg(ml::HipML{$T}, b::Vector{$T}; cycle::Cycle = V(), maxiter::Int = len
     x, hist[1:iters[] + 1]
 end
 
+# the same cg on each column of an n x bs block (bs = the workspace's block size, 1..64), all on the block cycle in one call:
+# independent cg's, not block CG.  Keeps min(maxiter, 10000) + 1 history entries per column.
+function cg(ml::HipML{$T}, B::Matrix{$T}; cycle::Cycle = V(), maxiter::Int = size(B, 1), abstol = 0.0,
+            reltol = sqrt(eps($T)))
+    bs = size(B, 2)
+    bs == ml.workspace.bs ||
+        throw(DimensionMismatch("hierarchy was uploaded with block size $(ml.workspace.bs), B has $bs columns"))
+    ldh = min(maxiter, 10000) + 1
+    X = zeros($T, size(B)); hist = zeros($T, ldh, bs); iters = zeros(Cint, bs)
+    check(ccall((:amgh_pcg_block, $lib), Cint,
+                (Ptr{Cvoid}, Ptr{$T}, Ptr{$T}, Cint, Cint, Cint, Float64, Float64, Ptr{$T}, Cint, Ptr{Cint}),
+                ml.workspace.handle, B, X, cyclecode(cycle), 1, maxiter, abstol, reltol, hist, ldh, iters))
+    X, [hist[1:min(iters[j], ldh - 1) + 1, j] for j in 1:bs]
+end
+
 end # @eval
 end # for (T, lib)
 
