@@ -15,7 +15,7 @@ The directory name contains a dot, so import it through the repo-root alias:
 """
 from ._libs import AMGError, gpu_available, hip_lib, setup_lib  # noqa: F401
 from .sparse import SparseMatrixCSC  # noqa: F401
-from .smoothers import (BackwardSweep, ForwardSweep, GaussSeidel, Jacobi, SingularException, SOR,  # noqa: F401
+from .smoothers import (BackwardSweep, Chebyshev, ForwardSweep, GaussSeidel, Jacobi, SingularException, SOR,  # noqa: F401
                         SymmetricSweep)
 from .hierarchy import (Classical, DenseLUFactorization, HermitianSymmetry, JacobiProlongation, Level,  # noqa: F401
                         LinearSolveWrapper, LocalWeighting, SuperLUFactorization,
@@ -25,7 +25,7 @@ from .hierarchy import (Classical, DenseLUFactorization, HermitianSymmetry, Jaco
 from .solve import (AMGSolver, F, Identity, Preconditioner, RugeStubenAMG, RugeStubenPreconBuilder,  # noqa: F401
                     SmoothedAggregationAMG, SmoothedAggregationPreconBuilder, V, W, _solve, _solve_inplace,
                     aspreconditioner, cg, gmres, init, solve, solve_)
-from .device import DeviceBuffer, DeviceCSR, DeviceHierarchy  # noqa: F401
+from .device import DeviceBuffer, DeviceCSR, DeviceHierarchy, approximate_spectral_radius  # noqa: F401
 from . import sharded  # noqa: F401
 
 __all__ = [n for n in dir() if not n.startswith("__")]

@@ -119,6 +119,12 @@ def _bind_solve_phase(L, creal, coarse_fn):
     L.amgh_set_coarse.argtypes = [vp, i64, vp, vp, vp, vp]
     L.amgh_set_coarse_host.argtypes = [vp, i64, vp, vp, vp, coarse_fn, vp]
     L.amgh_finalize.argtypes = [vp]
+    L.amgh_set_chebyshev_bounds.argtypes = [vp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int]
+    L.amgh_chebyshev_bounds.argtypes = [vp, C.c_int, C.c_int, f64p, f64p]
+    L.amgh_chebyshev_coefficients.argtypes = [C.c_int, C.c_double, C.c_double, vp]
+    L.amgh_level_spectral_radius.argtypes = [vp, C.c_int, C.c_int, f64p]
+    L.amgh_csr_spectral_radius.argtypes = [vp, C.c_int, f64p, vp]
+    L.amgh_csr_chebyshev_d.argtypes = [vp, C.c_int, C.c_double, C.c_double, vp, vp, vp, vp]
     L.amgh_num_levels.argtypes = [vp]
     L.amgh_tail_dense_build.argtypes = [vp, C.c_int]
     L.amgh_tail_dense_info.argtypes = [vp, C.c_int, C.POINTER(C.c_int), C.POINTER(i64), C.POINTER(C.c_double)]

@@ -14,6 +14,7 @@
 #include "amghip_internal.hpp"
 #include "gs_schedule.hpp"
 #include "csr_ops.hpp"
+#include "chebyshev.hpp"
 #include "gmres_kernels.hpp"
 #include "pcg_block_kernels.hpp"
 
@@ -27,6 +28,9 @@ struct Level {
   bool has_S = false;  // S distinct from A
   amgh_smoother_t pre{}, post{};
   real *res = nullptr, *cx = nullptr, *cb = nullptr, *tmp = nullptr;
+  real* cheb_d = nullptr;   // a Chebyshev side: the polynomial's direction vector (n x workspace columns), beside tmp
+  ChebSide cheb[2];         // [0] pre, [1] post: bounds and coefficients (chebyshev.hpp)
+  const ChebSide& cheb_of(const amgh_smoother_t& s) const { return &s == &post ? cheb[1] : cheb[0]; }
   real* il = nullptr;   // blocks of right-hand sides: interleaved copy of what R / P gather (max(n, nc) x bs)
   amgh_csr* smat() { return has_S ? &S : &A; }
   // level-ordered cycle (x stays in the smoother's dependency-level order between pre- and post-smoother):
@@ -200,6 +204,19 @@ int smooth(amgh_t* h, Level* L, const amgh_smoother_t& s, real*& xc, real*& xo, 
         else RC_TRY(csr_jacobi(M, s.omega, xc, b, xo, h->stream, ncolv));
         std::swap(xc, xo);
         break;
+      case AMGH_SMOOTH_CHEBYSHEV: {
+        // s.sweep = the degree; one pass over the matrix per step, x ping-ponging as Jacobi's does.  The polynomial restarts
+        // with every repetition: its first step writes d without reading it.
+        const ChebSide& cs = L->cheb_of(s);
+        if ((int)cs.c.size() != 2 * s.sweep || !L->cheb_d || !xo) return AMGH_ESTATE;
+        for (int k = 0; k < s.sweep; ++k) {
+          const real c1 = (real)cs.c[2 * (size_t)k], c2 = (real)cs.c[2 * (size_t)k + 1];
+          if (k == 0 && xzero && it == 0 && g_jacobi_zero) RC_TRY(csr_chebyshev_zero(M, c2, b, L->cheb_d, xo, h->stream, ncolv));   // x = 0: no matrix pass
+          else RC_TRY(csr_chebyshev(M, c1, c2, k == 0, xc, b, L->cheb_d, xo, h->stream, ncolv));
+          std::swap(xc, xo);
+        }
+        break;
+      }
       case AMGH_SMOOTH_GS:
       case AMGH_SMOOTH_SOR: {
         const bool sor = s.kind == AMGH_SMOOTH_SOR;
@@ -838,8 +855,9 @@ int check_ready(const amgh_t* h) {
 
 bool smoother_valid(const amgh_smoother_t* s) {
   if (!s) return false;
-  if (s->kind < AMGH_SMOOTH_NONE || s->kind > AMGH_SMOOTH_SOR) return false;
+  if (s->kind < AMGH_SMOOTH_NONE || s->kind > AMGH_SMOOTH_CHEBYSHEV) return false;
   if (s->iter < 0) return false;
+  if (s->kind == AMGH_SMOOTH_CHEBYSHEV && (s->sweep < 1 || s->sweep > kChebMaxDegree)) return false;   // sweep = the degree
   if ((s->kind == AMGH_SMOOTH_GS || s->kind == AMGH_SMOOTH_SOR) &&
       (s->sweep < AMGH_SWEEP_FORWARD || s->sweep > AMGH_SWEEP_SYMMETRIC)) return false;
   return true;
@@ -909,7 +927,7 @@ void amgh_destroy(amgh_t* h) {
   if (h->pending_level) level_discard(h->pending_level);
   for (Level* L : h->levels) {
     csr_free(&L->A); csr_free(&L->S); csr_free(&L->P); csr_free(&L->R); csr_free(&L->Pp); csr_free(&L->Rp);
-    hipFree(L->res); hipFree(L->cx); hipFree(L->cb); hipFree(L->tmp); hipFree(L->lo_val); hipFree(L->il);
+    hipFree(L->res); hipFree(L->cx); hipFree(L->cb); hipFree(L->tmp); hipFree(L->cheb_d); hipFree(L->lo_val); hipFree(L->il);
     L->lo_cc.free_dev();
     delete L;
   }
@@ -1274,11 +1292,97 @@ int amgh_set_coarse_host(amgh_t* h, int64_t n, const int32_t* A_rowptr, const in
   return AMGH_OK;
 }
 
+// Bounds and coefficients of a level's Chebyshev sides (amgh_finalize): sides whose bounds came as factors get them from ONE
+// estimate of the spectral radius of D^-1 S per level; the operator's value-coded columns are built where it qualifies.
+static int level_chebyshev_setup(amgh_t* h, Level* L) {
+  amgh_csr* M = L->smat();
+  double rho = 0.0;
+  bool have = false;
+  for (int side = 0; side < 2; ++side) {
+    const amgh_smoother_t& s = side ? L->post : L->pre;
+    if (s.kind != AMGH_SMOOTH_CHEBYSHEV) continue;
+    ChebSide& cs = L->cheb[side];
+    if (cs.relative) {
+      if (!have) { RC_TRY(csr_spectral_radius(M, kLanczosSteps, 0, h->stream, &rho)); have = true; }
+      cs.lo *= rho; cs.hi *= rho; cs.relative = false;
+    }
+    if (!cheb_bounds_valid(cs.lo, cs.hi)) return AMGH_EINVAL;
+    cs.c.assign(2 * (size_t)s.sweep, 0.0);
+    cheb_coefficients(s.sweep, cs.lo, cs.hi, cs.c.data());
+  }
+  if (M->col && M->val) RC_TRY(csr_ensure_coded(M, h->stream));
+  return AMGH_OK;
+}
+
+int amgh_set_chebyshev_bounds(amgh_t* h, int level, int post, double lo, double hi, int relative) {
+  if (!h || level < 0 || (post != 0 && post != 1)) return AMGH_EINVAL;
+  if (h->finalized) return AMGH_ESTATE;
+  Level* L = level < (int)h->levels.size() ? h->levels[level] : (level == (int)h->levels.size() ? h->pending_level : nullptr);
+  if (!L) return AMGH_EINVAL;
+  if ((post ? L->post : L->pre).kind != AMGH_SMOOTH_CHEBYSHEV) return AMGH_EINVAL;
+  if (!cheb_bounds_valid(lo, hi)) return AMGH_EINVAL;
+  ChebSide& cs = L->cheb[post];
+  cs.lo = lo; cs.hi = hi; cs.relative = relative != 0;
+  return AMGH_OK;
+}
+
+int amgh_chebyshev_bounds(const amgh_t* h, int level, int post, double* lo, double* hi) {
+  if (!h || level < 0 || level >= (int)h->levels.size() || (post != 0 && post != 1)) return AMGH_EINVAL;
+  if (!h->finalized) return AMGH_ESTATE;
+  const Level* L = h->levels[level];
+  if ((post ? L->post : L->pre).kind != AMGH_SMOOTH_CHEBYSHEV) return AMGH_EINVAL;
+  if (lo) *lo = L->cheb[post].lo;
+  if (hi) *hi = L->cheb[post].hi;
+  return AMGH_OK;
+}
+
+int amgh_chebyshev_coefficients(int degree, double lo, double hi, double* c1c2) {
+  if (degree < 1 || degree > kChebMaxDegree || !c1c2 || !cheb_bounds_valid(lo, hi)) return AMGH_EINVAL;
+  cheb_coefficients(degree, lo, hi, c1c2);
+  return AMGH_OK;
+}
+
+int amgh_level_spectral_radius(amgh_t* h, int level, int steps, double* rho) {
+  RC_TRY(check_ready(h));
+  if (level < 0 || level >= (int)h->levels.size() || !rho || steps < 0) return AMGH_EINVAL;
+  HIP_TRY(hipSetDevice(h->device));
+  amgh_csr* M = h->levels[level]->smat();
+  if (!M->rowptr || !M->col || !M->val) return AMGH_EINVAL;   // (released by the trimmed footprint)
+  return csr_spectral_radius(M, steps ? steps : kLanczosSteps, 0, h->stream, rho);
+}
+
+int amgh_csr_spectral_radius(amgh_csr_t* op, int steps, double* rho, void* stream) {
+  if (!op || !rho || steps < 0) return AMGH_EINVAL;
+  HIP_TRY(hipSetDevice(op->device));
+  return csr_spectral_radius(op, steps ? steps : kLanczosSteps, 0, (hipStream_t)stream, rho);
+}
+
+int amgh_csr_chebyshev_d(amgh_csr_t* op, int degree, double lo, double hi, real* x_d, const real* b_d, real* work_d, void* stream) {
+  if (!op || !x_d || !b_d || !work_d || op->nrows != op->ncols) return AMGH_EINVAL;
+  if (degree < 1 || degree > kChebMaxDegree || !cheb_bounds_valid(lo, hi)) return AMGH_EINVAL;
+  HIP_TRY(hipSetDevice(op->device));
+  hipStream_t st = (hipStream_t)stream;
+  RC_TRY(csr_ensure_coded(op, st));
+  double c[2 * kChebMaxDegree];
+  cheb_coefficients(degree, lo, hi, c);
+  const int64_t n = op->nrows;
+  real *xc = x_d, *xo = work_d, *d = work_d + n;
+  for (int k = 0; k < degree; ++k) {
+    RC_TRY(csr_chebyshev(op, (real)c[2 * k], (real)c[2 * k + 1], k == 0, xc, b_d, d, xo, st));
+    std::swap(xc, xo);
+  }
+  if (xc != x_d) HIP_TRY(hipMemcpyAsync(x_d, xc, sizeof(real) * n, hipMemcpyDeviceToDevice, st));
+  return AMGH_OK;
+}
+
 int amgh_finalize(amgh_t* h) {
   if (!h) return AMGH_EINVAL;
   if (h->finalized || h->ncoarse < 0 || h->pending_level) return AMGH_ESTATE;
   if (h->levels.empty() && !h->has_finalA) return AMGH_ESTATE;
   HIP_TRY(hipSetDevice(h->device));
+  // Chebyshev sides first: a refused estimate or pair of bounds leaves the handle as it was (amgh_set_chebyshev_bounds, then again)
+  for (Level* L : h->levels)
+    if (L->pre.kind == AMGH_SMOOTH_CHEBYSHEV || L->post.kind == AMGH_SMOOTH_CHEBYSHEV) RC_TRY(level_chebyshev_setup(h, L));
   int64_t ws = 0;
   // the collapsed coarse tail: the first level of at most tail_dense_rows rows (with a device coarse solver below it); its
   // operator is built later (tail_dense_build), from blocks of tail_cols right-hand sides — the workspaces of the tail's
@@ -1304,10 +1408,15 @@ int amgh_finalize(amgh_t* h) {
       RC_TRY(dev_alloc(&L->il, std::max(L->n, L->nc) * h->nrhs));
       ws += kRealB * std::max(L->n, L->nc) * h->nrhs;
     }
-    if (L->pre.kind == AMGH_SMOOTH_JACOBI || L->post.kind == AMGH_SMOOTH_JACOBI) {
+    const bool cheb = L->pre.kind == AMGH_SMOOTH_CHEBYSHEV || L->post.kind == AMGH_SMOOTH_CHEBYSHEV;
+    if (L->pre.kind == AMGH_SMOOTH_JACOBI || L->post.kind == AMGH_SMOOTH_JACOBI || cheb) {
       RC_TRY(dev_alloc(&L->tmp, L->n * wc));
       ws += kRealB * L->n * wc;
       RC_TRY(csr_ensure_diag(L->smat(), h->stream));
+    }
+    if (cheb) {
+      RC_TRY(dev_alloc(&L->cheb_d, L->n * wc));
+      ws += kRealB * L->n * wc;
     }
   }
   // value-coded columns of the big operators the level-ordered cycle streams (its A, Rp, Pp: everything is in its final order
@@ -1523,7 +1632,9 @@ int amgh_debug_coded_ops(const amgh_t* h, int l) {
   const GsSchedule* g = (L->has_S ? L->S : L->A).gs;
   const bool a_on = L->lo_cc.ccol && (g_stream_code || (g && !g->col));
   const bool r_on = L->Rp.cc.ccol && (g_stream_code || !L->Rp.col), p_on = L->Pp.cc.ccol && (g_stream_code || !L->Pp.col);
-  return (a_on ? 1 : 0) | (r_on ? 2 : 0) | (p_on ? 4 : 0);
+  const amgh_csr& M = L->has_S ? L->S : L->A;   // natural order: what a Chebyshev smoother streams
+  const bool s_on = M.cc.ccol && (g_stream_code || !M.col);
+  return (a_on ? 1 : 0) | (r_on ? 2 : 0) | (p_on ? 4 : 0) | (s_on ? 8 : 0);
 }
 int amgh_gs_num_dependency_levels(const amgh_t* h, int l) {
   if (!h || l < 0 || l >= (int)h->levels.size()) return -1;
@@ -1900,7 +2011,7 @@ static int level_smooth_enqueue(amgh_t* h, int level, int post, real* x_d, const
   const amgh_smoother_t& s = post ? L->post : L->pre;
   real* xc = x_d;
   real* xo = L->tmp;
-  if (s.kind == AMGH_SMOOTH_JACOBI && !xo) return AMGH_ESTATE;
+  if ((s.kind == AMGH_SMOOTH_JACOBI || s.kind == AMGH_SMOOTH_CHEBYSHEV) && !xo) return AMGH_ESTATE;
   RC_TRY(smooth(h, L, s, xc, xo, b_d));
   if (xc != x_d) RC_TRY(vec_copy(h, x_d, xc, L->n));
   return AMGH_OK;
@@ -1923,7 +2034,7 @@ int amgh_debug_level_smooth_block_d(amgh_t* h, int level, int post, real* x_d, c
   HIP_TRY(hipSetDevice(h->device));
   Level* L = h->levels[level];
   const amgh_smoother_t& s = post ? L->post : L->pre;
-  if (s.kind == AMGH_SMOOTH_JACOBI && !L->tmp) return AMGH_ESTATE;
+  if ((s.kind == AMGH_SMOOTH_JACOBI || s.kind == AMGH_SMOOTH_CHEBYSHEV) && !L->tmp) return AMGH_ESTATE;
   real* xc = x_d;
   real* xo = L->tmp;
   RC_TRY(smooth(h, L, s, xc, xo, b_d, h->nrhs));

@@ -1032,6 +1032,8 @@ int amgh_dist_push_level(amgh_dist_t* d, int64_t n_global, int64_t nc_global, co
   if (!d || !row_cuts || !crow_cuts || !A_rowptr || !P_rowptr || !R_rowptr || n_global <= 0 || nc_global < 0)
     return AMGH_EINVAL;
   if (!smoother_valid(pre) || !smoother_valid(post)) return AMGH_EINVAL;
+  // the Chebyshev polynomial smoother is single-GPU so far (its bounds would need the estimate across the shards)
+  if (pre->kind == AMGH_SMOOTH_CHEBYSHEV || post->kind == AMGH_SMOOTH_CHEBYSHEV) return AMGH_EUNSUPPORTED;
   if (d->finalized) return AMGH_ESTATE;
   if (n_global >= INT32_MAX || nc_global >= INT32_MAX) return AMGH_EUNSUPPORTED;
   const int N = d->tr->nranks, me = d->tr->rank;

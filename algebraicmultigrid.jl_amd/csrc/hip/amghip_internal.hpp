@@ -372,6 +372,7 @@ struct CodedCols {
 
 struct amgh_csr {
   CodedCols cc;
+  bool cc_tried = false;  // csr_ensure_coded has looked at this operator (natural-order operators of Chebyshev smoothers)
   bool xcd_map = false;   // SpMV launches of this operator with the XCD-contiguous mapping of the workgroups (amgh_finalize times both)
   int device = 0;
   int64_t nrows = 0, ncols = 0, nnz = 0;
@@ -397,7 +398,7 @@ int g_gs_super = 8;             // block-inverse sweeps: blocks per superblock (
 int g_gs_coarse_lo = 1;         // level-ordered cycle: hand the coarse vectors of a level over in the next level's order (read at amgh_push_level)
 int g_gs_bigslot = 1;           // allow long-row slots (composite rows up to 2048 entries) when merging
 int g_gs_merge = 16;             // merged-level sweeps: largest group of dependency levels tried (1 = off); read at schedule build
-int g_jacobi_zero = 1;          // Jacobi on x = 0 as a vector kernel (0 = the full sweep); read at every sweep
+int g_jacobi_zero = 1;          // Jacobi — and the first step of a Chebyshev polynomial — on x = 0 as a vector kernel (0 = the full sweep); read at every sweep
 int g_rhs_il = 1;               // blocks of 2 / 4 / 8 / 16 right-hand sides: restriction and prolongation gather an interleaved copy of their input (0 = column by column); read at every cycle
 int g_gs_tiny = 1;              // an operator that fits LDS entirely: 1 = gs_wave_kernel where its record was built, else gs_chain_tiny_kernel; 2 = gs_chain_tiny_kernel; 0 = gs_chain_kernel; read at every sweep
 int g_gs_wave_quad = 1;         // the single-wave walk with four lanes per row where its record was built (gs_waveq_kernel: a row's additions as four interleaved partial sums); 0 = one lane per row (the scalar loop's bits); read at schedule build (0: not built) and at every sweep

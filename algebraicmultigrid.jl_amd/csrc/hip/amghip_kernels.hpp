@@ -37,8 +37,13 @@ enum StreamMode : int {
   M_ADD = 2,     // y = y + A x            (multilevel.jl:233-234)
   M_JACOBI = 3,  // damped Jacobi sweep    (smoother.jl:113-141)
   M_GS = 4,      // Gauss-Seidel rows of one dependency level (smoother.jl:61-90)
-  M_SOR = 5      // SOR rows of one dependency level           (smoother.jl:193-221)
+  M_SOR = 5,     // SOR rows of one dependency level           (smoother.jl:193-221)
+  M_CHEB1 = 6,   // first step of a Chebyshev polynomial: d = c2 D^-1 (b - S x), y = x + d (d is written, never read)
+  M_CHEB = 7     // later steps: d = c1 d + c2 D^-1 (b - S x), y = x + d
 };
+// the smoothers whose row sum leaves the diagonal entry out / that write x through the dependency-level permutation
+template <int MODE> constexpr bool kSkipDiag = MODE >= M_JACOBI && MODE <= M_SOR;
+template <int MODE> constexpr bool kLevelRows = MODE == M_GS || MODE == M_SOR;
 
 struct StreamArgs {
   const int32_t* rowptr;  // CSR of the (possibly level-permuted) matrix
@@ -63,6 +68,10 @@ struct StreamArgs {
   const uint32_t* ccol;
   const real* vtab;
   int32_t vtab_n;
+  // Chebyshev steps (M_CHEB1 / M_CHEB): the direction vector (ncolv columns, ldd apart) and the step's two coefficients
+  real* d;
+  int64_t ldd;
+  real c1, c2;
 };
 constexpr int kCodeBits = 24, kCodeMax = 256;
 typedef unsigned int u4_t __attribute__((ext_vector_type(4)));
@@ -196,6 +205,7 @@ __global__ __launch_bounds__(CFG::THREADS) void csr_stream_kernel(StreamArgs a) 
     a.x += cv * a.ldx;
     a.y += cv * a.ldy;
     if (a.b) a.b += cv * a.ldb;
+    if (MODE >= M_CHEB1) a.d += cv * a.ldd;
   }
 
   const int nrows = a.row_end - a.row_begin;
@@ -215,8 +225,8 @@ __global__ __launch_bounds__(CFG::THREADS) void csr_stream_kernel(StreamArgs a) 
     if (tid + q * T < CFG::ROWS && r < r1) {
       rs[q] = a.rowptr[r];
       re[q] = a.rowptr[r + 1];
-      dp[q] = (MODE >= M_JACOBI) ? a.dpos[r] : -1;
-      if (MODE >= M_GS) {  // issued up front: independent of the products, off the critical path
+      dp[q] = kSkipDiag<MODE> ? a.dpos[r] : -1;
+      if (kLevelRows<MODE>) {  // issued up front: independent of the products, off the critical path
         gi[q] = a.perm ? a.perm[r] : r;  // x in dependency-level order: row r writes position r
         gd[q] = a.diag[r];
         gb[q] = a.b[r];  // b pre-gathered into dependency-level order
@@ -282,8 +292,8 @@ __global__ __launch_bounds__(CFG::THREADS) void csr_stream_kernel(StreamArgs a) 
 #pragma unroll
     for (int q = 0; q < RPT; ++q) {
       const int lo = max(rs[q], c0), hi = min(re[q], c1);
-      if (SK) acc[q] = seq_sum<(MODE >= M_JACOBI)>(s_prod, lo, hi, c0, dp[q], acc[q]);
-      else acc[q] = seq_sum_skip(s_prod, lo - c0, hi - c0, (MODE >= M_JACOBI) ? dp[q] - c0 : -1, acc[q]);
+      if (SK) acc[q] = seq_sum<kSkipDiag<MODE>>(s_prod, lo, hi, c0, dp[q], acc[q]);
+      else acc[q] = seq_sum_skip(s_prod, lo - c0, hi - c0, kSkipDiag<MODE> ? dp[q] - c0 : -1, acc[q]);
     }
     if (c1 < p1) __syncthreads();
   }
@@ -303,6 +313,14 @@ __global__ __launch_bounds__(CFG::THREADS) void csr_stream_kernel(StreamArgs a) 
       const real t = a.x[r];
       const real cand = (1.0 - a.omega) * t + a.omega * ((a.b[r] - acc[q]) / d);
       a.y[r] = (d == 0.0) ? t : cand;
+    } else if (MODE == M_CHEB1 || MODE == M_CHEB) {
+      // the whole row sum (diagonal included): t = D^-1 (b - S x); a row without a diagonal keeps its x and gets d = 0
+      const real dg = a.diag[r];
+      const real t = a.x[r];
+      real dn = a.c2 * ((a.b[r] - acc[q]) / dg);
+      if (MODE == M_CHEB) dn = a.c1 * a.d[r] + dn;
+      a.d[r] = (dg == 0.0) ? (real)0.0 : dn;
+      a.y[r] = (dg == 0.0) ? t : t + dn;
     } else {
       const int i = gi[q];
       const real d = gd[q];
@@ -976,6 +994,22 @@ __global__ void jacobi_zero_kernel(const real* __restrict__ b, const real* __res
     const real d = diag[r];
     const real cand = (1.0 - omega) * t + omega * ((b[r] - acc) / d);
     y[r] = (d == 0.0) ? t : cand;
+  }
+}
+
+// The first Chebyshev step on x = 0 (the same places): d = c2 ((b - 0) / diag), y = 0 + d — the expression the stream kernel
+// evaluates in mode M_CHEB1 with a row sum of +0, bitwise, as a vector kernel.  gridDim.y = right-hand-side columns.
+__global__ void cheb_zero_kernel(const real* __restrict__ b, const real* __restrict__ diag, real* __restrict__ y, real* __restrict__ d,
+                                 int64_t n, real c2, int64_t ldb, int64_t ldy, int64_t ldd) {
+  b += blockIdx.y * ldb;
+  y += blockIdx.y * ldy;
+  d += blockIdx.y * ldd;
+  const real t = 0.0, acc = 0.0;
+  for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < n; r += (int64_t)gridDim.x * blockDim.x) {
+    const real dg = diag[r];
+    const real dn = c2 * ((b[r] - acc) / dg);
+    d[r] = (dg == 0.0) ? (real)0.0 : dn;
+    y[r] = (dg == 0.0) ? t : t + dn;
   }
 }
 

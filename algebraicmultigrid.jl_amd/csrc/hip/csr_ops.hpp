@@ -197,6 +197,39 @@ int csr_jacobi_zero(amgh_csr* op, real omega, const real* b, real* xout, hipStre
   return AMGH_OK;
 }
 
+// One step of a Chebyshev polynomial smoother (csr_stream_kernel, M_CHEB1 / M_CHEB): per row t = (b - S x) / diag over the WHOLE
+// row, d = c1 d + c2 t (first: d = c2 t, d is not read), xout = xin + d; rows without a diagonal keep x and get d = 0.  One pass
+// over the matrix, through its value-coded columns where the operator has them (csr_ensure_coded) — the same products in the
+// same order.  d: nrows per column.
+int csr_chebyshev(amgh_csr* op, real c1, real c2, bool first, const real* xin, const real* b, real* d, real* xout, hipStream_t st,
+                  int ncolv = 1) {
+  RC_TRY(csr_ensure_diag(op, st));
+  StreamArgs a{};
+  a.rowptr = op->rowptr; a.col = op->col; a.val = op->val;
+  a.ccol = op->cc.ccol; a.vtab = op->cc.vtab; a.vtab_n = op->cc.n;
+  a.x = xin; a.y = xout; a.b = b; a.diag = op->diag; a.d = d; a.c1 = c1; a.c2 = c2;
+  a.row_begin = 0; a.row_end = (int32_t)op->nrows;
+  a.ldx = op->ncols; a.ldy = op->nrows; a.ldb = op->nrows; a.ldd = op->nrows;
+  return first ? launch_stream_sized<M_CHEB1>(a, st, ncolv) : launch_stream_sized<M_CHEB>(a, st, ncolv);
+}
+// the first step from x = 0: no matrix pass (cheb_zero_kernel)
+int csr_chebyshev_zero(amgh_csr* op, real c2, const real* b, real* d, real* xout, hipStream_t st, int ncolv = 1) {
+  RC_TRY(csr_ensure_diag(op, st));
+  if (op->nrows > 0)
+    hipLaunchKernelGGL(cheb_zero_kernel, dim3((unsigned)std::min<int64_t>((op->nrows + 255) / 256, 1 << 20), ncolv), dim3(256), 0, st,
+                       b, (const real*)op->diag, xout, d, (int64_t)op->nrows, c2, (int64_t)op->nrows, (int64_t)op->nrows, (int64_t)op->nrows);
+  HIP_TRY(hipGetLastError());
+  return AMGH_OK;
+}
+// value-coded columns of a natural-order operator a Chebyshev smoother streams (once per operator; synchronises st: setup time only)
+int csr_ensure_coded(amgh_csr* op, hipStream_t st) {
+  if (op->cc_tried || !g_stream_code) return AMGH_OK;
+  op->cc_tried = true;
+  RC_TRY(code_values(op->col, op->val, op->nrows, op->ncols, op->nnz, &op->cc, st));
+  op->bytes += op->cc.bytes;
+  return AMGH_OK;
+}
+
 template <int T, int PF>
 int launch_chain_t(const ChainArgs& c, bool sor, bool ldsx, int nx, hipStream_t st, int ncolv) {
   if (sor && ldsx) hipLaunchKernelGGL((gs_chain_kernel<true, true, T, PF>), dim3(ncolv), dim3(T), 0, st, c, nx);

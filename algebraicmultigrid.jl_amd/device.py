@@ -111,6 +111,12 @@ class DeviceCSR:
         self.sync()
         return yd.download()
 
+    def spectral_radius(self, steps=0):
+        """amgh_csr_spectral_radius: Lanczos estimate of the spectral radius of D⁻¹M (steps = 0: the default, 15)."""
+        rho = C.c_double(0.0)
+        hip_check(self.lib.amgh_csr_spectral_radius(self.h, int(steps), C.byref(rho), None), "csr_spectral_radius")
+        return rho.value
+
     def smooth(self, config, x, b):
         """Run `config.iter` sweeps in place on host vector x (returns new x)."""
         n = self.nrows
@@ -118,7 +124,15 @@ class DeviceCSR:
         bd = DeviceBuffer(n, self.device, b, dtype=self.dtype)
         tmp = DeviceBuffer(self.ncols, self.device, x, dtype=self.dtype) if config.kind == 2 else None
         cur, other = xd, tmp
+        if config.kind == 4:
+            if self.nrows != self.ncols:
+                raise AMGError("Chebyshev: the operator must be square")
+            lo, hi = config.bounds(self.spectral_radius() if config.rho is None else None)
+            work = DeviceBuffer(2 * n, self.device, dtype=self.dtype)
         for _ in range(config.iter):
+            if config.kind == 4:
+                hip_check(self.lib.amgh_csr_chebyshev_d(self.h, config.degree, lo, hi, cur.ptr, bd.ptr, work.ptr, None), "chebyshev")
+                continue
             if config.kind == 2:
                 hip_check(self.lib.amgh_csr_jacobi_d(self.h, config.omega, cur.ptr, bd.ptr, other.ptr, None), "jacobi")
                 cur, other = other, cur
@@ -153,6 +167,15 @@ def smooth_standalone(config, A, x, b, symmetry=None, dtype=np.float64):
     rp, ci, va = smoother_matrix_csr(A, symmetry)
     op = DeviceCSR(A.m, A.n, rp, ci, va, dtype=dtype)
     x[...] = op.smooth(config, np.asarray(x, dtype=dtype), np.asarray(b, dtype=dtype))
+
+
+def approximate_spectral_radius(A, symmetry=None, steps=15, device=0):
+    """Estimate of the spectral radius of D⁻¹S, S the matrix a smoother would sweep for `symmetry`: a `steps`-step Lanczos
+    process on the device (symmetric S with a positive diagonal; never above the true value).  What `Chebyshev()` without
+    `rho` takes its bounds from."""
+    A = SparseMatrixCSC.coerce(A)
+    rp, ci, va = smoother_matrix_csr(A, symmetry)
+    return DeviceCSR(A.m, A.n, rp, ci, va, device=device).spectral_radius(steps)
 
 
 class DeviceHierarchy:
@@ -291,6 +314,12 @@ class DeviceHierarchy:
             self._coarse_cb = (COARSE_FN if self.dtype.itemsize == 8 else COARSE_FN_F32)(_cb)
             hip_check(self.lib.amgh_set_coarse_host(self.h, fA.m, _ptr(fr), _ptr(fc), _ptr(fv), self._coarse_cb, None),
                       "set_coarse_host")
+        # Chebyshev sides: their bounds (absolute with rho given, else factors of the estimate amgh_finalize makes)
+        for l, lev in enumerate(ml.levels):
+            for post, sm in enumerate((lev.presmoother, lev.postsmoother)):
+                if getattr(sm, "kind", 0) == 4:
+                    lo, hi, rel = sm.c_bounds()
+                    hip_check(self.lib.amgh_set_chebyshev_bounds(self.h, l, post, lo, hi, rel), "set_chebyshev_bounds")
         hip_check(self.lib.amgh_finalize(self.h), "finalize")
         # the collapsed coarse tail's operator for V-cycles now, inside the setup (W / F: at their first cycle)
         hip_check(self.lib.amgh_tail_dense_build(self.h, 0), "tail_dense_build")
@@ -394,6 +423,18 @@ class DeviceHierarchy:
             return self.ml.final_A.m
         lev = self.ml.levels[level]
         return lev.P.n if which == OP_R else lev.A.m
+
+    def chebyshev_bounds(self, level, post=0):
+        """(lo, hi) the level's Chebyshev side runs with."""
+        lo, hi = C.c_double(0.0), C.c_double(0.0)
+        hip_check(self.lib.amgh_chebyshev_bounds(self.h, level, int(post), C.byref(lo), C.byref(hi)), "chebyshev_bounds")
+        return lo.value, hi.value
+
+    def spectral_radius(self, level, steps=0):
+        """amgh_level_spectral_radius of the level's smoother matrix."""
+        rho = C.c_double(0.0)
+        hip_check(self.lib.amgh_level_spectral_radius(self.h, level, int(steps), C.byref(rho)), "level_spectral_radius")
+        return rho.value
 
     def smooth(self, level, post, x, b):
         x = np.array(x, dtype=self.dtype, copy=True)

@@ -56,12 +56,12 @@ typedef struct amgh_csr amgh_csr_t; /* one CSR operator on HBM                  
 
 /* smoother configuration: GaussSeidel{Sweep}(sweep, iter) smoother.jl:17-23,
  * Jacobi(omega; iter) :92-99, SOR(omega, sweep, iter) :173-180                  */
-enum { AMGH_SMOOTH_NONE = 0, AMGH_SMOOTH_GS = 1, AMGH_SMOOTH_JACOBI = 2, AMGH_SMOOTH_SOR = 3 };
+enum { AMGH_SMOOTH_NONE = 0, AMGH_SMOOTH_GS = 1, AMGH_SMOOTH_JACOBI = 2, AMGH_SMOOTH_SOR = 3, AMGH_SMOOTH_CHEBYSHEV = 4 };
 enum { AMGH_SWEEP_FORWARD = 0, AMGH_SWEEP_BACKWARD = 1, AMGH_SWEEP_SYMMETRIC = 2 };
 typedef struct {
   int32_t kind;  /* AMGH_SMOOTH_*                                               */
-  int32_t sweep; /* AMGH_SWEEP_* (GS, SOR)                                      */
-  int32_t iter;  /* number of sweeps (>= 0)                                     */
+  int32_t sweep; /* AMGH_SWEEP_* (GS, SOR); Chebyshev: the degree, 1..16        */
+  int32_t iter;  /* number of sweeps (>= 0); Chebyshev: repetitions             */
   int32_t pad_;
   double omega;  /* Jacobi / SOR damping                                        */
 } amgh_smoother_t;
@@ -167,6 +167,36 @@ int amgh_set_coarse_host(amgh_t* h, int64_t n, const int32_t* A_rowptr, const in
 /* Allocates the workspace (res_vecs, coarse_xs, coarse_bs), builds the
  * Gauss-Seidel dependency schedules.  Must be called once before any solve.     */
 int amgh_finalize(amgh_t* h);
+
+/* The Chebyshev polynomial smoother (AMGH_SMOOTH_CHEBYSHEV; no reference counterpart: PyAMG's, hypre's and AmgX's polynomial
+ * relaxation).  For the level's smoother matrix S, D = diag(S) and bounds 0 < lo < hi on the eigenvalues of D^-1 S:
+ *   theta = (hi + lo) / 2, delta = (hi - lo) / 2, sigma = theta / delta, rho = 1 / sigma
+ *   d = (1 / theta) D^-1 (b - S x);  x += d
+ *   k = 2 .. degree:  rho' = 1 / (2 sigma - rho);  d = (rho' rho) d + (2 rho' / delta) D^-1 (b - S x);  x += d;  rho = rho'
+ * `iter` repeats the whole polynomial; rows whose diagonal is zero or missing keep their x (as smoother.jl:87,137).  One fused
+ * pass over the matrix per step, the same arithmetic for one right-hand side and for a block; symmetric (pre and post the same
+ * polynomial: a valid cg preconditioner).  amgh_smoother_t keeps its layout: `sweep` carries the degree (1..16), `iter` the
+ * repetitions, `omega` is ignored; the bounds travel through amgh_set_chebyshev_bounds, per level and side (post = 0 | 1),
+ * between that level's push (amgh_push_level, _begin or _prepared: level = the index it has or will have) and amgh_finalize:
+ *   relative = 0: lo, hi are the eigenvalue bounds themselves;
+ *   relative = 1: factors of an estimate rho_est of the spectral radius of D^-1 S made at amgh_finalize (lo * rho_est, hi *
+ *                 rho_est) — what a side gets that is never set, with lo = 1 / 30, hi = 1.1 (PyAMG's defaults).
+ * The estimate (amgh_level_spectral_radius below) assumes S symmetric with a positive diagonal; for other operators give the
+ * bounds.  AMGH_EINVAL: degree outside 1..16 (at push), lo <= 0, lo >= hi, non-finite bounds, a side that is not Chebyshev,
+ * and — from amgh_finalize, which then leaves the handle unfinalized and otherwise untouched — an estimate that is not a
+ * positive number (an all-zero diagonal).  Row-sharded levels refuse the kind (amgh_dist_push_level: AMGH_EUNSUPPORTED).    */
+int amgh_set_chebyshev_bounds(amgh_t* h, int level, int post, double lo, double hi, int relative);
+/* the eigenvalue bounds a finalized level's side runs with                                                          */
+int amgh_chebyshev_bounds(const amgh_t* h, int level, int post, double* lo, double* hi);
+/* The (c1, c2) pairs of the steps above, c1c2[2 k] = c1 and c1c2[2 k + 1] = c2 of step k + 1 (c1 of step 1 is 0): host
+ * only, in double — the numbers the kernels are launched with.                                                     */
+int amgh_chebyshev_coefficients(int degree, double lo, double hi, double* c1c2);
+/* *rho = the largest Ritz value in magnitude of a `steps`-step Lanczos process (0 = the default, 15; clamped to n) for D^-1 S
+ * in the D-inner product, S = level's smoother matrix: three-term recurrence on the device (the level's SpMV, deterministic
+ * sums, start vector U[0,1) from the splitmix64 stream with seed 0: the same number at every call), the tridiagonal
+ * eigenproblem on the host.  Assumes S symmetric with a positive diagonal; a Ritz value never exceeds the spectrum.
+ * AMGH_EINVAL when the result is not positive and finite.                                                          */
+int amgh_level_spectral_radius(amgh_t* h, int level, int steps, double* rho);
 
 int amgh_num_levels(const amgh_t* h);            /* length(ml.levels)            */
 /* The collapsed coarse tail.  The reference recurses through its small levels for free (__solve!, multilevel.jl:214-239, the
@@ -303,6 +333,13 @@ int amgh_csr_spmv_add_d(amgh_csr_t* op, const amgh_real* x_d, amgh_real* y_d, vo
  * included), xout nrows.                                                        */
 int amgh_csr_jacobi_d(amgh_csr_t* op, double omega, const amgh_real* xin_d, const amgh_real* b_d,
                       amgh_real* xout_d, void* stream);
+/* One Chebyshev polynomial of `degree` steps (see amgh_set_chebyshev_bounds) on a square operator, in place on x_d; lo, hi:
+ * the eigenvalue bounds; work_d: 2 * nrows reals of device scratch.  Streams the operator's value-coded columns where it
+ * qualifies (>= 2^18 rows, at most 256 distinct values; built at the first call, which then synchronises the stream).  */
+int amgh_csr_chebyshev_d(amgh_csr_t* op, int degree, double lo, double hi, amgh_real* x_d, const amgh_real* b_d,
+                         amgh_real* work_d, void* stream);
+/* amgh_level_spectral_radius for a stand-alone square operator; synchronises `stream`.                              */
+int amgh_csr_spectral_radius(amgh_csr_t* op, int steps, double* rho, void* stream);
 /* Gauss-Seidel / SOR sweep in exact lexicographic order over the leading
  * nrows x nrows block (columns >= nrows are halo entries held fixed);
  * backward != 0 sweeps n..1.  omega = 1 is Gauss-Seidel (smoother.jl:61-90),
@@ -589,7 +626,8 @@ int amgh_debug_bw_late(const amgh_t* h, int l);
  * entry: column | code << 24, the code an index into the operator's table of distinct values — built at amgh_finalize for
  * operators of >= 2^18 rows, fewer than 2^24 columns and at most 256 distinct values; the sums are the plain kernel's, bit
  * for bit; tunable "stream_code"): bit 0 = A (residual, multilevel.jl:219-220), bit 1 = R (restriction, :221), bit 2 = P
- * (prolongation, :233-234).  -1: no such level.                                                                       */
+ * (prolongation, :233-234), bit 3 = the smoother matrix in natural order (the steps of a Chebyshev smoother; with S == A the
+ * residual of such a level too).  -1: no such level.                                                                  */
 int amgh_debug_coded_ops(const amgh_t* h, int l);
 
 /* Diagnostics: tunables of the Gauss-Seidel execution and the cycle (process-wide; used by tools/ to pick the defaults and
@@ -599,7 +637,8 @@ int amgh_debug_coded_ops(const amgh_t* h, int l);
  * single-wave walk with four lanes per row where its record was built; 0: one lane per row, the scalar loop's bits),
  * "gs_lpr" / "gs_ept" (lanes per row / entries per thread of merged slot launches, 0 = by shape), "gs_il" (blocks of
  * right-hand sides: merged groups gather from an interleaved copy), "gs_sell" (merged groups from the SELL-like layout),
- * "gs_dense_tri" (small operators through the dense inverse of the whole triangle), "jacobi_zero", "rhs_il", and
+ * "gs_dense_tri" (small operators through the dense inverse of the whole triangle), "jacobi_zero" (Jacobi and the first
+ * Chebyshev step on x = 0 as a vector kernel), "rhs_il", and
  * "gs_merge" <= 1 / "gs_block_inverse" = 0 to bypass already-built merged groups / block-inverse data.  Read when a
  * schedule is BUILT (amgh_push_level, first stand-alone sweep of an operator): "gs_merge" (largest group of dependency
  * levels tried), "gs_bigslot" (0 off, 1 cost model, 2 always), "gs_super" (blocks per superblock), "gs_block_inverse",

@@ -45,6 +45,32 @@ csmoother(s::FastJacobiSmoother) = CSmoother(2, 2, s.iter, 0, Float64(s.ω))
 csmoother(s::FastSORSmoother{S}) where {S} = CSmoother(3, sweepcode(S()), s.iter, 0, Float64(s.ω))
 # NoSymmetry caches map to the same kernels on the true rows (S == A); see amgh_push_level.
 
+# The Chebyshev polynomial smoother (AMGH_SMOOTH_CHEBYSHEV = 4; no counterpart in AlgebraicMultigrid.jl): `sweep` carries the degree,
+# `iter` the repetitions.  rho === nothing: lower / upper are factors of the estimate amgh_finalize makes of the spectral radius of
+# D^-1 S (symmetric operators); otherwise the eigenvalue bounds are lower * rho, upper * rho.
+struct Chebyshev
+    degree::Int; lower::Float64; upper::Float64; iter::Int; rho::Union{Nothing,Float64}
+end
+Chebyshev(; degree = 3, lower = 1 / 30, upper = 1.1, iter = 1, rho = nothing) = Chebyshev(degree, lower, upper, iter, rho)
+csmoother(s::Chebyshev) = CSmoother(4, s.degree, s.iter, 0, 0.0)
+# between the level's push and amgh_finalize; level 0-based, post = 0 | 1
+function set_chebyshev_bounds!(lib, handle::Ptr{Cvoid}, level::Integer, post::Integer, s::Chebyshev)
+    lo, hi, rel = s.rho === nothing ? (s.lower, s.upper, 1) : (s.lower * s.rho, s.upper * s.rho, 0)
+    check(ccall((:amgh_set_chebyshev_bounds, lib), Cint, (Ptr{Cvoid}, Cint, Cint, Cdouble, Cdouble, Cint), handle, level, post, lo, hi, rel))
+end
+# the (c1, c2) pairs of the polynomial's steps, from the library's own definition
+function chebyshev_coefficients(lib, degree::Integer, lo::Real, hi::Real)
+    c = Vector{Float64}(undef, 2 * degree)
+    check(ccall((:amgh_chebyshev_coefficients, lib), Cint, (Cint, Cdouble, Cdouble, Ptr{Float64}), degree, lo, hi, c))
+    [(c[2k - 1], c[2k]) for k in 1:degree]
+end
+# Lanczos estimate of the spectral radius of D^-1 S of a pushed level (steps = 0: 15)
+function approximate_spectral_radius(lib, handle::Ptr{Cvoid}, level::Integer; steps::Integer = 0)
+    rho = Ref{Float64}(0.0)
+    check(ccall((:amgh_level_spectral_radius, lib), Cint, (Ptr{Cvoid}, Cint, Cint, Ref{Float64}), handle, level, steps, rho))
+    rho[]
+end
+
 """
 Workspace type that marks a MultiLevel as resident on the GPU (replaces MultiLevelWorkspace{TX,bs}); `T` is the
 arithmetic type of the handle = the instance of the library it lives in (Float64: libamghip, Float32: libamghip_f32).
