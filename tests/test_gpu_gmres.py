@@ -12,6 +12,7 @@ import scipy.sparse as sp
 import amg_amd as AMG
 import gmres_ref as G
 from conftest import ROOT
+from krylov_cases import upwind
 from oracle import oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -27,23 +28,6 @@ def issue95():
     rng = np.random.default_rng(95)
     N = 10000
     return sp.random(N, N, 0.001, random_state=rng, format="csc") + 5 * sp.identity(N, format="csc")
-
-
-def upwind(m, dim, eps=0.01, v=(1.0, 0.6, 0.3)):
-    """-eps Laplacian + first-order upwind v . grad on the unit square / cube, m points per direction, Dirichlet."""
-    h = 1.0 / (m + 1)
-    I = sp.identity(m, format="csr")
-    lap = sp.diags([-1.0, 2.0, -1.0], [-1, 0, 1], shape=(m, m), format="csr") / h**2
-    d = sp.diags([-1.0, 1.0], [-1, 0], shape=(m, m), format="csr") / h
-    terms = []
-    for axis in range(dim):
-        ops = [I] * dim
-        ops[axis] = eps * lap + v[axis] * d
-        t = ops[0]
-        for o in ops[1:]:
-            t = sp.kron(t, o, format="csr")
-        terms.append(t)
-    return sp.csc_matrix(sum(terms))
 
 
 def check_against_checker(A, ml, b, cycle="V", restart=None, reltol=None, maxiter=None, xtol=1e-8, htol=1e-8):

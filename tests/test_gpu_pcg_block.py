@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import amg_amd as AMG
+from krylov_cases import block
 from oracle import oracle as O
 from shipping_defaults import shipping_defaults
 
@@ -40,15 +41,6 @@ def hierarchy(name):
     if name not in _ml:
         _ml[name] = BUILDERS[name]()
     return _ml[name]
-
-
-def block(n, bs, seed=7):
-    """bs right-hand sides with different shapes and scales (column j of a wider block is the same column)."""
-    rng = np.random.default_rng(seed)
-    B = rng.standard_normal((n, max(bs, 16)))
-    B[:, 1] = np.sin(np.arange(n) * 0.37) + 2.0
-    B[:, 2] *= 1e3
-    return np.asfortranarray(B[:, :bs])
 
 
 def oracle_pcg(name, b, cycle, **kw):
