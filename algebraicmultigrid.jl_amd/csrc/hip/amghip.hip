@@ -2595,6 +2595,17 @@ int amgh_debug_get_tunable(const char* name, int* value) {
   return AMGH_OK;
 }
 
+// The switch of the order changes folded into the relayed sweeps (csr_gs_sweep, gs_relay.hpp PB / PX): read at every sweep.
+int amgh_debug_set_perm_io(int on) {
+  g_gs_flow_perm_io = on != 0;
+  ++g_sched_epoch;   // captured cycles bake the execution path in: every handle captures again after a change
+  return AMGH_OK;
+}
+int amgh_debug_get_perm_io(void) { return g_gs_flow_perm_io; }
+// Sweeps launched so far with b read through the permutation (which = 0) / with x written in natural order too (1): what a test
+// reads before and after a call to know that the call ran them (a captured cycle counts when it is captured, not when replayed).
+int amgh_debug_perm_io_sweeps(int which) { return (which == 0 || which == 1) ? (int)(g_perm_io_sweeps[which] & 0x7fffffffu) : -1; }
+
 int amgh_debug_chain_timing(int enable, unsigned long long* out8) {
   if (enable && !g_chain_tim) {
     HIP_TRY(hipMalloc((void**)&g_chain_tim, 8 * sizeof(unsigned long long)));

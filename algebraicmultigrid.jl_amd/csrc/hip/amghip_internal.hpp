@@ -416,6 +416,8 @@ int g_gs_bw_inorder = 0;        // 1: the relayed single-column sweep sums every
 int g_gs_bw_dict = 1;           // the relayed single-column sweep reads the dictionary layout where a schedule carries one (bw::FlowDict: half the bytes of a 7-point level's sweep; bitwise the same); read at schedule build (0: not built) and at every sweep
 int g_gs_bw_relay = 3;          // walker waves a single-column dataflow sweep relays a block's walk between (gs_relay.hpp: the one instantiated count, BW_RELAY_W; 0: one walker, gs_bw_flow_kernel — bitwise the same); read at every sweep
 int g_gs_flow_xzero = 1;        // a dataflow sweep that starts a smooth! call on x = 0 reads no x (0: fill + read as any other sweep — bitwise the same); read at every sweep
+int g_gs_flow_perm_io = 1;      // the relayed sweep that starts / ends a single-column smooth! call reads b through the permutation / writes x in natural order too (0: gather_perm_kernel and scatter_perm_kernel — bitwise the same); amgh_debug_set_perm_io, read at every sweep
+unsigned int g_perm_io_sweeps[2] = {0, 0};  // sweeps launched with b read through the permutation / with x written in natural order too (amgh_debug_perm_io_sweeps: what a test asks to know that a case ran them)
 int g_gs_bw_two_min_rows = 200000;  // wavefront of blocks: operators with TWO offset classes (2-D grids) take it from this many rows where the cost model agrees (0 = never); round 4: 6 000 000; with the relayed dataflow sweep 512^2 / 1024^2 / 2048^2 Poisson V-cycles 4.82 -> 3.92 / 9.35 -> 8.50 / 21.6 -> 18.3 ms, 4096^2 39.1 -> 39.9 (profiles/r05_block_layout_threshold.log); read at schedule build
 int g_gs_sell = 1;              // merged groups from the SELL-like layout where it was built (0 = slot kernels); build: read at schedule build too
 int g_gs_lean = -1;             // footprint policy: -1 = AMGH_LEAN environment variable (unset: trim), 0 = full (every copy kept), 1 = lean, 2 = trim; read at schedule build

@@ -702,8 +702,20 @@ int csr_gs_sweep(amgh_csr* op, bool backward, bool sor, real omega, real* x, con
     g->bytes += (int64_t)sizeof(real) * xs * ncolv; op->bytes += (int64_t)sizeof(real) * xs * ncolv;
     g->xil_cols = 0;
   }
+  // The order changes of a smooth! call folded into its sweeps (switch amgh_debug_set_perm_io, gs_relay.hpp PB / PX): where the sweep is the
+  // relayed dataflow kernel on this very schedule — one column, a square operator, no merged child system, not a sweep of a row-sharded
+  // level pipelined across the ranks — the sweep that runs first reads b through the permutation (and leaves the level-ordered copy
+  // behind for the residual and the later sweeps), the sweep that runs last stores x in natural order as well.  (The natural-order
+  // vectors are addressed through one buffer descriptor each: up to 2 GB.)
+  const bool perm_io = g_gs_flow_perm_io && ncolv == 1 && g->ncols == g->n && lay == g && !op->pipe_epoch && g_gs_bw_relay > 0 &&
+                       g->bw.on && g->bw.flow.on && (g_gs_bw_flow || !g->bw.rec) &&
+                       (int64_t)sizeof(real) * g->n < 0x7ffffff0ll;
+  const bool fuse_b = perm_io && first && !(reuse_b && g->bp_cols == ncolv);
+  // (the last sweep keeps its blocks' slices of the permutation in LDS: where the largest block has no room for it, the scatter kernel)
+  const bool fuse_x = perm_io && last && !no_scatter && bw::relay_perm_x_ok<real>(g->bw.maxk, g->bw.flow.dict_on && (g_gs_bw_dict || !g->bw.flow.srec)) &&
+                      ((g->bw.flow.dict_on && (g_gs_bw_dict || !g->bw.flow.srec)) ? g->bw.flow.dict_lds : g->bw.flow.lds_max) + bw::relay_perm_lds<real>(g->bw.flow.lds_max) <= 64 * 1024;
   if (first) {
-    if (!(reuse_b && g->bp_cols == ncolv))
+    if (!(reuse_b && g->bp_cols == ncolv) && !fuse_b)
       hipLaunchKernelGGL(gather_perm_kernel, dim3(grid_for(g->n), ncolv), dim3(256), 0, st, b, g->perm, g->bp, (int)g->n,
                          (int64_t)g->n, (int64_t)g->n);
     g->bp_cols = ncolv;
@@ -818,6 +830,12 @@ int csr_gs_sweep(amgh_csr* op, bool backward, bool sor, real omega, real* x, con
         fa.grid = g->bw.maxk > 6 ? (dict ? 0 : kBwGridLong) : kBwGrid;
         fa.late = (g->bw.flow.late_ok && !g_gs_bw_inorder) ? 1 : 0;   // the dependency-aware row sum (gs_relay.hpp, LATE)
         if (dict) { fa.crec = g->bw.flow.crec; fa.dict = g->bw.flow.dict; fa.dict_ent = g->bw.flow.dict_ent; }
+        if (fuse_b) { fa.perm_b = g->perm; fa.b_nat = b; }
+        if (fuse_x) { fa.perm_x = g->perm; fa.x_nat = x; }
+        if (fuse_b || fuse_x) {
+          e = bw::sweep_relay_io<real>(fa, g->bw.maxk, dict ? g->bw.flow.dict_lds : g->bw.flow.lds_max, g->bw.flow.lds_max, sor, backward, st);
+          g_perm_io_sweeps[0] += fuse_b ? 1u : 0u; g_perm_io_sweeps[1] += fuse_x ? 1u : 0u;
+        } else
         e = bw::sweep_relay<real>(fa, g->bw.maxk, dict ? g->bw.flow.dict_lds : g->bw.flow.lds_max, sor, backward, st, BW_RELAY_W);
       } else {
         if (dict) {
@@ -956,7 +974,7 @@ int csr_gs_sweep(amgh_csr* op, bool backward, bool sor, real omega, real* x, con
       if (il) RC_TRY(il_copy_rows(ncolv, xp, xs, g->xil, a.row_begin, a.row_end - a.row_begin, st));
     }
   }
-  if (last && !no_scatter) {
+  if (last && !no_scatter && !fuse_x) {
     hipLaunchKernelGGL(scatter_perm_kernel, dim3(grid_for(g->n), ncolv), dim3(256), 0, st, (const real*)xp, g->perm, x,
                        (int)g->n, xs, (int64_t)g->n);
     HIP_TRY(hipGetLastError());

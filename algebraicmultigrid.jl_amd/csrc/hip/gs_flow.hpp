@@ -463,6 +463,9 @@ struct FlowArgs {
   const void* rmbox = nullptr;       // mailboxes of the neighbouring rank this sweep's halo entries come from (peer-mapped; fetch-list entries with kRemoteCell set)
   int32_t late = 0;                  // the relayed kernel sums the far half of every row above the hand-over (records with the split entry layout; host side only)
   int32_t grid = 0;                  // workgroups to launch: fewer than blocks = the persistent form (host side only; 0: one per block)
+  // the order changes of a smooth! call folded into its first and its last sweep (gs_relay.hpp, template flags PB / PX; null: not asked for)
+  const int32_t* perm_b = nullptr; const R* b_nat = nullptr;   // b[r] = b_nat[perm_b[r]] is made by the sweep itself: every block fills its rows of b (written, then) before it reads them
+  const int32_t* perm_x = nullptr; R* x_nat = nullptr;         // every computed row goes to x_nat[perm_x[r]] as well as to x[r]
 };
 
 template <typename R> struct Mail;

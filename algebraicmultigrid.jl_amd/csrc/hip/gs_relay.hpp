@@ -18,6 +18,13 @@
 // *err — is gs_flow.hpp's.  Per row the arithmetic is unchanged: bitwise the scalar loop.
 // Template flag DICT: the records on the dictionary layout (gs_flow.hpp FlowDict) — a set in flight is the row's column chunks
 // and b, the values come out of the block's dictionary in LDS ahead of the hand-over (256^3: 0.61 -> 0.56 / 0.93 -> 0.78 ms).
+// Template flags PB / PX (sweep_relay_io): the two order changes of a smooth! call done by its first / last sweep instead of by
+// kernels of their own.  PB: in its load phase every walker wave brings the b of ITS steps' rows out of the caller's natural-order
+// vector (b_nat[perm_b[r]]) and stores it into the level-ordered one — the copy the residual and the later sweeps read —, then
+// streams it from there as ever (its own stores, waited for before the first counted load: nothing new in the walk).  PX: the
+// block's slice of the permutation is loaded into LDS with the block (behind its dictionary: 4 bytes per row), and a computed row
+// is stored a second time, to x_nat[perm_x[r]], behind the publish and the store of x — one more counted store per step; the
+// index is read out of LDS there, behind the hand-over's critical path, so no register lives across it for this.
 #pragma once
 #include "gs_flow.hpp"
 
@@ -79,7 +86,7 @@ __device__ __forceinline__ unsigned lds_addr(const void* p) { return (unsigned)(
 // loop's bits (tunable gs_bw_inorder = 1 keeps those) and more than one reassociation: the pre-scaling rounds every near
 // product twice.  What holds per row, and tests/sweep_bound.py asserts: |x_i - x*_i| <= (m_i + 4) u (|omega| (|b_i| +
 // sum |a_ik x_k|) / |a_ii| + |1 - omega| |x_old,i|), x* the exact update from the same inputs, m_i the row's off-diagonals.
-template <typename R, bool SOR, bool BWD, int MAXK, int W, bool DICT, bool LATE>
+template <typename R, bool SOR, bool BWD, int MAXK, int W, bool DICT, bool LATE, bool PB, bool PX>
 __device__ __forceinline__ void relay_block(const FlowArgs<R>& a, unsigned char* lds_all, const int wv, const int lane, const unsigned int ut,
                                             const unsigned int epoch, const long long t_start) {
   typedef typename std::conditional<DICT, FlowOpsD<R, MAXK>, FlowOps<R, MAXK>>::type O;
@@ -284,6 +291,7 @@ __device__ __forceinline__ void relay_block(const FlowArgs<R>& a, unsigned char*
   const i32x4 rs_b = make_rsrc(a.b + d.row0);
   const i32x4 rs_x = make_rsrc(x + d.row0);
   const i32x4 rs_mst = make_rsrc(a.mbox);
+  const i32x4 rs_xn = make_rsrc(PX ? a.x_nat : nullptr);   // (PX) x in natural order
   // operands of walking step kk (one of mine) into o; steps behind the last one: a harmless re-read of the block's first chunk
   auto issue = [&](O& o, int kk) {
     const unsigned w = (unsigned)__builtin_amdgcn_readfirstlane((int)sw_next);
@@ -309,6 +317,7 @@ __device__ __forceinline__ void relay_block(const FlowArgs<R>& a, unsigned char*
     asm_load<RB / 4>(o.bb, (unsigned)tt * RB, rs_b, (unsigned)r0 * RB);
   };
   O ops[D];
+  int perm_off = 0;   // (PX) the block's slice of the permutation in LDS: behind the control words and the dictionary
   {
     // the walkers' half of the load phase: the block's own rows into LDS, a share each
     constexpr int XW = W >= 4 ? 2 : 4;
@@ -330,6 +339,41 @@ __device__ __forceinline__ void relay_block(const FlowArgs<R>& a, unsigned char*
       const u32x4* dg = (const u32x4*)(a.dict + (size_t)(de & 0xffffff) * 16);
       u32x4* dl = (u32x4*)(lds + nxb + 16);
       for (int i = wv * 64 + lane; i < nchunk; i += 64 * W) dl[i] = dg[i];
+      perm_off = nchunk * 16;
+    }
+    if constexpr (PX) {
+      perm_off += nxb + 16;
+      const int32_t* pg = a.perm_x + d.row0;
+      int32_t* pl = (int32_t*)(lds + perm_off);
+      for (int p = wv * 64 + lane; p < d.nrows; p += 64 * W) pl[p] = pg[p];
+    }
+    if constexpr (PB) {
+      // b of my steps' rows (the rows my own loads of b read, nobody else's) out of the natural-order vector into the level-ordered one:
+      // a few steps' index loads, then their gathers, in flight at once; the stores are waited for below, with everything else
+      constexpr int SB = 4;
+      const int32_t* pm = a.perm_b + d.row0;
+      const R* bn = uniform_ptr(a.b_nat);
+      R* bl = const_cast<R*>(a.b) + d.row0;
+      for (int k0 = wv; k0 < ns; k0 += W * SB) {
+        int pr[SB]; bool on[SB]; int32_t pi[SB]; R bv[SB];
+#pragma unroll
+        for (int k = 0; k < SB; ++k) {
+          const int kk = k0 + k * W;
+          const unsigned w = axc[kk < ns ? kk : ns];   // (word ns: no rows)
+          const int r0 = (int)(w & ((1u << kStepRowBits) - 1)), nr = (int)((w >> kStepRowBits) & ((1u << kStepCntBits) - 1));
+          on[k] = lane < nr;
+          pr[k] = on[k] ? r0 + lane : 0;
+          pi[k] = pm[pr[k]];
+        }
+#pragma unroll
+        for (int k = 0; k < SB; ++k) pin(pi[k]);
+#pragma unroll
+        for (int k = 0; k < SB; ++k) bv[k] = bn[pi[k]];
+#pragma unroll
+        for (int k = 0; k < SB; ++k) pin(bv[k]);
+#pragma unroll
+        for (int k = 0; k < SB; ++k) if (on[k]) bl[pr[k]] = bv[k];
+      }
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // (nothing of the compiler's in flight when the counted loads start)
 #pragma unroll
@@ -346,6 +390,7 @@ __device__ __forceinline__ void relay_block(const FlowArgs<R>& a, unsigned char*
   const unsigned xl_base = (unsigned)__builtin_amdgcn_readfirstlane((int)lds_addr(xl));
   const unsigned ctl_off = xl_base + (unsigned)nxb;   // (LDS address of the control words)
   const unsigned dict_base = ctl_off + 16u;            // (the dictionary layout: the block's distinct value rows)
+  const unsigned perm_base = xl_base + (unsigned)__builtin_amdgcn_readfirstlane(perm_off);   // (PX: the rows' natural indices)
 #ifdef BW_RELAY_STAMPS   // (measurement builds: three wall-clock stamps per step in LDS behind the control words, dumped at the end;
   // per mailbox the time its row was published (a counted third store of the step) and the time its reader's fetcher saw it)
   const unsigned stamp_base = xl_base + (unsigned)nxb + 16u;
@@ -555,20 +600,23 @@ __device__ __forceinline__ void relay_block(const FlowArgs<R>& a, unsigned char*
       asm_store_sc1(cv, cell, rs_mst);
       u32x2 xv2 = {qlo, qhi};
       asm_store(xv2, xoff, rs_x);
+      if constexpr (PX) asm_store(xv2, lds_get<unsigned>(perm_base + (unsigned)o.p * 4u) * (unsigned)RB, rs_xn);
     } else {
       u32x2 cv = {__float_as_uint(q), epoch};
       asm_store_sc1(cv, cell, rs_mst);
       asm_store(__float_as_uint(q), xoff, rs_x);
+      if constexpr (PX) asm_store(__float_as_uint(q), lds_get<unsigned>(perm_base + (unsigned)o.p * 4u) * (unsigned)RB, rs_xn);
     }
 #ifdef BW_FLOW_STEP_STAMPS
     if (a.tim && lane == 0) a.tim[4 * (int64_t)a.nblocks + 128 * (int64_t)ob + kk] = wall_clock64();
 #endif
   };
   // The pipeline of gs_flow.hpp over MY steps (j-th one: wv + j W): D register sets, vmcnt counted exactly per wave
+  // (PX: one store more per step)
 #ifdef BW_RELAY_STAMPS
-  constexpr int L = O::NLOAD, S = 3;
+  constexpr int L = O::NLOAD, S = 3 + (PX ? 1 : 0);
 #else
-  constexpr int L = O::NLOAD, S = 2;
+  constexpr int L = O::NLOAD, S = 2 + (PX ? 1 : 0);
 #endif
   const int nsw = ns > wv ? (ns - wv + W - 1) / W : 0;
   int k = 0;
@@ -621,10 +669,13 @@ __device__ __forceinline__ void relay_block(const FlowArgs<R>& a, unsigned char*
 // tickets until they run out.  That is what several sweeps sharing one device need (the ranks of a row-sharded level on a
 // single GPU: a workgroup of rank p may wait for values of rank p - 1, whose workgroups must then BE resident, not queued
 // behind it), and what bounds the resident workgroups of a launch.  A launch of one workgroup per block is the plain form.
-template <typename R, bool SOR, bool BWD, int MAXK, int W, bool DICT = false, bool LATE = false>
+template <typename R, bool SOR, bool BWD, int MAXK, int W, bool DICT = false, bool LATE = false, bool PB = false, bool PX = false>
 __global__ __launch_bounds__(64 * (W + 1), DICT ? RelayWavesD<MAXK>::value : RelayWaves<MAXK>::value) void gs_bw_relay_kernel(FlowArgs<R> a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_all[];
   static_assert(W >= 2 && W <= 7, "walker waves per block");
+#ifdef BW_RELAY_STAMPS
+  static_assert(!PX, "the stamps of a measurement build lie where the slice of the permutation goes");
+#endif
   const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const int lane = (int)(threadIdx.x & 63u);
   const unsigned int units = (unsigned int)a.nblocks;
@@ -645,7 +696,7 @@ __global__ __launch_bounds__(64 * (W + 1), DICT ? RelayWavesD<MAXK>::value : Rel
       __hip_atomic_store(a.head, (unsigned long long)(sweeps + 2u >= 0x80000000u ? 0u : sweeps + 1u) << 32, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (ut >= units) return;
     const unsigned int epoch = a.epoch ? a.epoch : sweeps + 1u;   // (a.epoch: the tag of a sweep that several launches share, amghip_dist.hpp)
-    relay_block<R, SOR, BWD, MAXK, W, DICT, LATE>(a, lds_all, wv, lane, ut, epoch, t_start);
+    relay_block<R, SOR, BWD, MAXK, W, DICT, LATE, PB, PX>(a, lds_all, wv, lane, ut, epoch, t_start);
     if (!persistent) return;
     __syncthreads();   // (everybody is done with this block's LDS)
   }
@@ -655,9 +706,15 @@ static_assert(RelayDepth<6>::value <= 4 && RelayDepth<12>::value <= 4 && RelayDe
 // measurement knob: extra dynamic LDS per workgroup (bounds the blocks resident per CU)
 inline size_t& relay_lds_pad() { static size_t pad = 0; return pad; }
 
-template <typename R, bool SOR, bool BWD, int MAXK, int W, bool DICT = false, bool LATE = false>
+// (PX) LDS for a block's slice of the permutation, 4 bytes a row, from the LDS of the largest block's x (Flow::lds_max: sizeof(R) bytes
+// for every row and halo entry of the block, so at least sizeof(R) bytes a row): half of it where R has 8 bytes, all of it where 4
+template <typename R> inline size_t relay_perm_lds(size_t lds_x) {
+  static_assert(sizeof(R) == 4 || sizeof(R) == 8, "4 bytes a row out of sizeof(R) bytes a row");
+  return ((sizeof(R) == 8 ? (lds_x + 1) / 2 : lds_x) + 15) & ~(size_t)15;
+}
+template <typename R, bool SOR, bool BWD, int MAXK, int W, bool DICT = false, bool LATE = false, bool PB = false, bool PX = false>
 inline hipError_t sweep_relay_launch(const FlowArgs<R>& a, size_t lds, hipStream_t st) {
-  auto* fn = gs_bw_relay_kernel<R, SOR, BWD, MAXK, W, DICT, LATE>;
+  auto* fn = gs_bw_relay_kernel<R, SOR, BWD, MAXK, W, DICT, LATE, PB, PX>;
   if (relay_lds_pad()) {
     lds += relay_lds_pad();
     static hipError_t once = hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
@@ -736,6 +793,54 @@ inline hipError_t sweep_relay(const FlowArgs<R>& a, int maxk, size_t lds_max, bo
 #endif
 #ifdef BW_EXTRA_MAXK   // (tools: one more row length, e.g. the 35-entry rows of the third level of the 256^3 hierarchy)
     case BW_EXTRA_MAXK: return sweep_relay_w<R, BW_EXTRA_MAXK>(a, lds_max, sor, backward, w, st);
+#endif
+  }
+  return hipErrorInvalidValue;
+}
+
+// The same sweep with the order changes of its smooth! call folded in (template flags PB / PX): a.perm_b / a.b_nat set = the sweep
+// makes the level-ordered b itself, a.perm_x / a.x_nat set = it writes x in natural order too.  A dispatch of its own: sweep_relay
+// reaches none of these instantiations (and the assembly audits of it count the kernels they always counted).
+// Where PX is instantiated: everywhere but the Float32 kernels on the dictionary layout with rows of up to 12 entries — the smallest
+// kernels of the family (61-67 / 80 registers), which the extra store's address and data push over a step of the register file
+// (73-77 / 85: 7 -> 6 / 6 -> 5 waves per SIMD by the compiler's count, tools/relay_regs.py); those keep the scatter kernel.
+template <typename R, int MAXK, bool DICT> struct RelayPermX { static constexpr bool ok = !(sizeof(R) == 4 && DICT && MAXK <= 12); };
+template <typename R> inline bool relay_perm_x_ok(int maxk, bool dict) { return !(sizeof(R) == 4 && dict && maxk <= 12); }
+// lds_x: the LDS of the largest block's x and control words (Flow::lds_max), lds: that, or with the largest dictionary behind it
+template <typename R, int MAXK, bool PB, bool PX>
+inline hipError_t sweep_relay_io_k(const FlowArgs<R>& a0, size_t lds, size_t lds_x, bool sor, bool backward, hipStream_t st) {
+  constexpr int W = BW_RELAY_W;
+  if (PX) lds += relay_perm_lds<R>(lds_x);
+  FlowArgs<R> a = a0;
+  a.ncols = 1; a.ngroups = 1; a.lds_stride = 0;
+  auto go = [&](auto dict, auto late) -> hipError_t {
+    constexpr bool DC = decltype(dict)::value, LT = decltype(late)::value;
+    if constexpr (PX && !RelayPermX<R, MAXK, DC>::ok) return hipErrorInvalidValue;
+    else {
+      if (sor) return backward ? sweep_relay_launch<R, true, true, MAXK, W, DC, LT, PB, PX>(a, lds, st) : sweep_relay_launch<R, true, false, MAXK, W, DC, LT, PB, PX>(a, lds, st);
+      return backward ? sweep_relay_launch<R, false, true, MAXK, W, DC, LT, PB, PX>(a, lds, st) : sweep_relay_launch<R, false, false, MAXK, W, DC, LT, PB, PX>(a, lds, st);
+    }
+  };
+  if (a.crec) return a.late ? go(std::true_type(), std::true_type()) : go(std::true_type(), std::false_type());
+  return a.late ? go(std::false_type(), std::true_type()) : go(std::false_type(), std::false_type());
+}
+template <typename R, int MAXK>
+inline hipError_t sweep_relay_io_m(const FlowArgs<R>& a, size_t lds, size_t lds_x, bool sor, bool backward, hipStream_t st) {
+  const bool pb = a.perm_b != nullptr, px = a.perm_x != nullptr;
+  if (pb && (!a.b_nat || !a.b)) return hipErrorInvalidValue;
+  if (px && !a.x_nat) return hipErrorInvalidValue;
+  if (pb && px) return sweep_relay_io_k<R, MAXK, true, true>(a, lds, lds_x, sor, backward, st);
+  if (pb) return sweep_relay_io_k<R, MAXK, true, false>(a, lds, lds_x, sor, backward, st);
+  if (px) return sweep_relay_io_k<R, MAXK, false, true>(a, lds, lds_x, sor, backward, st);
+  return hipErrorInvalidValue;   // (nothing to fold in: sweep_relay)
+}
+template <typename R>
+inline hipError_t sweep_relay_io(const FlowArgs<R>& a, int maxk, size_t lds_max, size_t lds_x, bool sor, bool backward, hipStream_t st) {
+  switch (maxk) {
+    case 6: return sweep_relay_io_m<R, 6>(a, lds_max, lds_x, sor, backward, st);
+    case 12: return sweep_relay_io_m<R, 12>(a, lds_max, lds_x, sor, backward, st);
+#if BW_PLAN_MAXK >= 18
+    case 18: return sweep_relay_io_m<R, 18>(a, lds_max, lds_x, sor, backward, st);
 #endif
   }
   return hipErrorInvalidValue;

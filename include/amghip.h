@@ -670,6 +670,15 @@ int amgh_debug_set_tunable(const char* name, int value);
  * "tail_dense_rows" < 0 reads 0, the 0 / 1 switches read 0 or 1, "gs_bw_relay" reads the one instantiated count).
  * Returns AMGH_EINVAL for any other name (the retired ones included).                                             */
 int amgh_debug_get_tunable(const char* name, int* value);
+/* A switch of its own, read at every sweep (default 1): the relayed sweep that starts a single-column smooth! call on a
+ * square operator reads b through the schedule's permutation, the one that ends it writes x in natural order too; 0: a
+ * gather and a scatter kernel of their own — bitwise the same.  Setting it makes captured cycles capture again.
+ * amgh_debug_get_perm_io returns the stored 0 / 1.  amgh_debug_perm_io_sweeps(which): the sweeps launched so far (modulo
+ * 2^31) with b read through the permutation (which = 0) / with x written in natural order too (1); -1 for any other
+ * argument.  A captured cycle counts when it is captured, not when it is replayed.                                   */
+int amgh_debug_set_perm_io(int on);
+int amgh_debug_get_perm_io(void);
+int amgh_debug_perm_io_sweeps(int which);
 
 /* Replay whole cycles from captured hipGraphs (default off: measured no gain on MI355X for big hierarchies —
  * the cycle is GPU-latency-bound and the host runs far ahead — nor for small ones, whose kernels take >= 3 us each;

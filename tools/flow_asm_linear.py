@@ -11,7 +11,7 @@ registers parks a set in AGPRs or re-uses a register as a temporary, and the dat
 The check is a forward dataflow over the kernel's control-flow graph (basic blocks from the labels and s_branch /
 s_cbranch instructions of the gfx950 assembly): the state is, per load, the smallest number of younger vector memory
 operations over all paths; blocks are re-visited until nothing changes.
-usage: python tools/flow_asm_linear.py [source.hip] [name-filter]      exit code 0 = clean; one line per kernel."""
+usage: python tools/flow_asm_linear.py [source.hip | assembly.s] [name-filter]      exit code 0 = clean; one line per kernel."""
 import os
 import re
 import subprocess
@@ -116,17 +116,26 @@ def scan(lines):
     return [(blocks[k[0]][1][k[1]], v[2], blocks[v[0]][0]) for k, v in sorted(bad.items())], ninstr, len(dst)
 
 
-def main():
-    src = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "tools", "flow_inst.hip")
-    flt = sys.argv[2] if len(sys.argv) > 2 else ""
+def assembly_of(src):
+    """the gfx950 assembly of src as lines (None: it does not compile); a .s file made by the same command is read as it is"""
+    if src.endswith(".s"):
+        return open(src).read().split("\n")
     with tempfile.TemporaryDirectory() as tmp:
         out = os.path.join(tmp, "k.s")
         cmd = [HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "--cuda-device-only", "-S", "-o", out, src] + os.environ.get("AUDIT_HIP_FLAGS", "").split()
         r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
         if r.returncode != 0:
             print(r.stdout.decode(errors="replace")[-2000:])
-            return 2
-        text = open(out).read().split("\n")
+            return None
+        return open(out).read().split("\n")
+
+
+def main():
+    src = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "tools", "flow_inst.hip")
+    flt = sys.argv[2] if len(sys.argv) > 2 else ""
+    text = assembly_of(src)
+    if text is None:
+        return 2
     kernels, cur = {}, None
     for l in text:
         m = re.match(r"^(_ZN4amgh2bw1[78]gs_bw_(?:flow|relay)_kernel\w+):", l)
