@@ -225,6 +225,7 @@ def _bind_dist(L):
     L.amgh_dist_local_range.argtypes = [vp, C.c_int, i64p, i64p]
     L.amgh_dist_precond_apply_d.argtypes = [vp, vp, vp, C.c_int]
     L.amgh_dist_solve_d.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, vp, C.POINTER(C.c_int)]
+    L.amgh_dist_pcg_d.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, vp, C.POINTER(C.c_int)]
     L.amgh_dist_spmv_d.argtypes = [vp, C.c_int, vp, vp]
     L.amgh_dist_sync.argtypes = [vp]
     L.amgh_dist_barrier.argtypes = [vp]

@@ -17,6 +17,7 @@
 #include "chebyshev.hpp"
 #include "gmres_kernels.hpp"
 #include "pcg_block_kernels.hpp"
+#include "dist_pcg_kernels.hpp"
 
 namespace {
 

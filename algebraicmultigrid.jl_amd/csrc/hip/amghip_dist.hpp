@@ -443,6 +443,7 @@ struct amgh_dist {
   bool gs_pipe = true;                 // ... exact order as ONE pipelined sweep where the level allows it (DistLevel::Pipe::on), else the ranks in turn
   int nplans = 0;
   real *partial = nullptr, *scal = nullptr;
+  real *pc_u = nullptr, *pc_c = nullptr;  // amgh_dist_pcg_d (allocated by its first call): u [local | halo] — the SpMV's input —, c = A u
   int64_t ex_count = 0, ex_bytes = 0;  // halo exchanges / bytes sent by this rank since the last reset
   int overlap = 1;
 };
@@ -888,9 +889,10 @@ void dist_free(amgh_dist* d) {
   if (!d->host_only) {
     for (VecPlan& p : d->xplan) { d->tr->plan_detach(p); p.free_dev(); }
     hipFree(d->xt); hipFree(d->bt); hipFree(d->partial); hipFree(d->scal);
+    hipFree(d->pc_u); hipFree(d->pc_c);
     if (d->stream) hipStreamDestroy(d->stream);
   }
-  if (d->host_exec) { free(d->xt); free(d->bt); }
+  if (d->host_exec) { free(d->xt); free(d->bt); free(d->pc_u); free(d->pc_c); }
   delete d->tr;
   delete d;
 }
@@ -1686,6 +1688,213 @@ int amgh_dist_solve_d(amgh_dist_t* d, const real* b_loc_d, real* x_loc_d, int cy
   RC_TRY(d->tr->wait_stream(d->stream));
   return bw_err_check();   // (sharded levels and the tail sweep by dataflow kernels too: a poll give-up is this call's error)
 }
+
+namespace {
+
+// ---- cg(A, b; Pl) over the ranks (amgh_dist_pcg_d; kernels: dist_pcg_kernels.hpp) -------------------------------------------
+int dist_ensure_pcg_bufs(amgh_dist* d) {
+  if (d->pc_u) return AMGH_OK;
+  const VecPlan& p0 = d->xplan[0];
+  const int64_t n = p0.nloc(), nu = n + p0.nhalo();
+  int rc = AMGH_OK;
+  if (d->host_exec) {
+    d->pc_u = (real*)calloc((size_t)std::max<int64_t>(1, nu), sizeof(real));
+    d->pc_c = (real*)calloc((size_t)std::max<int64_t>(1, n), sizeof(real));
+    if (!d->pc_u || !d->pc_c) rc = AMGH_ENOMEM;
+    if (rc != AMGH_OK) { free(d->pc_u); free(d->pc_c); }
+  } else {
+    rc = dev_alloc(&d->pc_u, nu);
+    if (rc == AMGH_OK) rc = dev_alloc(&d->pc_c, n);
+    if (rc != AMGH_OK) { hipFree(d->pc_u); hipFree(d->pc_c); }
+  }
+  if (rc != AMGH_OK) d->pc_u = d->pc_c = nullptr;
+  return rc;
+}
+
+inline int dpcg_blocks(int64_t n) { return (int)std::max<int64_t>(1, std::min<int64_t>(kRedBlocks, (n + kThreads - 1) / kThreads)); }
+
+// this rank's sum from the nb per-block partials a kernel left in d->partial: summed in a fixed order on the device, read back
+// (the stream has drained when this returns)
+int dpcg_local_finish(amgh_dist* d, int nb, double* out) {
+  real v = 0.0;
+  hipLaunchKernelGGL(reduce_final_kernel, dim3(1), dim3(kThreads), 0, d->stream, (const real*)d->partial, nb, d->scal, 0);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(&v, d->scal, sizeof(real), hipMemcpyDeviceToHost, d->stream));
+  RC_TRY(d->tr->wait_stream(d->stream));
+  *out = (double)v;
+  return AMGH_OK;
+}
+// this rank's sum of x_i y_i over its n rows (host execution: accumulated in double, as dist_dot's host branch does)
+int dpcg_local_dot(amgh_dist* d, const real* x, const real* y, int64_t n, double* out) {
+  *out = 0.0;
+  if (n <= 0) return AMGH_OK;
+  if (d->host_exec) {
+    double acc = 0.0;
+    for (int64_t i = 0; i < n; ++i) acc += (double)x[i] * (double)y[i];
+    *out = acc;
+    return AMGH_OK;
+  }
+  const int nb = dpcg_blocks(n);
+  hipLaunchKernelGGL(dot_partial_kernel, dim3(nb), dim3(kThreads), 0, d->stream, x, y, n, d->partial);
+  return dpcg_local_finish(d, nb, out);
+}
+// u = c + beta u
+int dpcg_dir(amgh_dist* d, real* u, const real* c, double beta, int64_t n) {
+  if (n <= 0) return AMGH_OK;
+  if (d->host_exec) {
+    const real be = (real)beta;
+    for (int64_t i = 0; i < n; ++i) u[i] = c[i] + be * u[i];
+    return AMGH_OK;
+  }
+  hipLaunchKernelGGL(dpcg_dir_kernel, dim3(grid_for(n)), dim3(kThreads), 0, d->stream, u, c, beta, n);
+  HIP_TRY(hipGetLastError());
+  return AMGH_OK;
+}
+// x += alpha u, r -= alpha c; *rr = this rank's sum of the new r_i^2
+int dpcg_update(amgh_dist* d, real* x, const real* u, real* r, const real* c, double alpha, int64_t n, double* rr) {
+  *rr = 0.0;
+  if (n <= 0) return AMGH_OK;
+  if (d->host_exec) {
+    const real ap = (real)alpha, am = -(real)alpha;
+    double acc = 0.0;
+    for (int64_t i = 0; i < n; ++i) {
+      x[i] = x[i] + ap * u[i];
+      const real rn = r[i] + am * c[i];
+      r[i] = rn;
+      acc += (double)rn * (double)rn;
+    }
+    *rr = acc;
+    return AMGH_OK;
+  }
+  const int nb = dpcg_blocks(n);
+  hipLaunchKernelGGL(dpcg_update_kernel, dim3(nb), dim3(kThreads), 0, d->stream, x, u, r, c, alpha, n, d->partial);
+  return dpcg_local_finish(d, nb, rr);
+}
+
+// One all-reduce of {this rank's value, this rank's failure flag}.  A rank whose local work failed has skipped the rest of it
+// but still arrives here, where its neighbours wait; after the call *fail is non-zero on EVERY rank or on none — the only
+// places the recurrence may leave its loop.  *v comes back rounded to amgh_real (what dist_dot hands out): the same bits on
+// every rank.  The return value is the transport's own: a collective that failed has failed for every rank (the transports
+// break for good), so nobody waits in a later one.
+int dpcg_allreduce(amgh_dist* d, double* v, int* fail) {
+  double w[2] = {*fail ? 0.0 : *v, *fail ? 1.0 : 0.0};
+  RC_TRY(d->tr->allreduce(w, 2, false));
+  *v = (double)(real)w[0];
+  if (w[1] != 0.0 && !*fail) *fail = AMGH_ESTATE;
+  return AMGH_OK;
+}
+
+#define DPCG_DO(expr)                        \
+  do {                                       \
+    if (!fail) {                             \
+      const int rc_ = (expr);                \
+      if (rc_ != AMGH_OK) fail = rc_;        \
+    }                                        \
+  } while (0)
+
+// nothing is sharded: the owner of the (collapsed) hierarchy runs pcg_dev on it; the count and the history reach the other
+// ranks — which touch no vector — by all-reduce, 64 values at a time (the transports' limit)
+int dist_pcg_collapsed(amgh_dist* d, const real* b, real* x, int cyc, int use_precond, int maxiter, double abstol,
+                       double reltol, real* hist, int* iters, int fail) {
+  const bool owner = d->xplan[0].nloc() > 0;
+  int it = 0;
+  if (owner) {
+    if (!fail && !d->tail) fail = AMGH_ESTATE;
+    DPCG_DO(ensure_pcg_bufs(d->tail));
+    DPCG_DO(pcg_dev(d->tail, b, x, cyc, use_precond, maxiter, abstol, reltol, hist, &it));
+  }
+  double v[3] = {owner && !fail ? (double)it : 0.0, fail ? 1.0 : 0.0, hist ? 1.0 : 0.0};
+  RC_TRY(d->tr->allreduce(v, 3, false));
+  if (v[1] != 0.0) return AMGH_ESTATE;
+  it = (int)v[0];
+  if (v[2] != 0.0) {   // (a rank that asked for no history still takes part in the rounds the others wait in)
+    for (int i0 = 0; i0 <= it; i0 += 64) {
+      const int m = std::min(64, it + 1 - i0);
+      double w[64];
+      for (int k = 0; k < m; ++k) w[k] = (owner && hist) ? (double)hist[i0 + k] : 0.0;
+      RC_TRY(d->tr->allreduce(w, m, false));
+      if (hist) for (int k = 0; k < m; ++k) hist[i0 + k] = (real)w[k];
+    }
+  }
+  if (iters) *iters = it;
+  return AMGH_OK;
+}
+
+}  // namespace
+
+// cg(A, b; Pl = aspreconditioner(ml), abstol, reltol, maxiter) over the ranks, x0 = 0: pcg_dev's recurrence (IterativeSolvers.jl's)
+// on this rank's rows.  r lives in the level-0 b of the cycle and Pl r is read where the cycle leaves it (the level-0 x): the
+// preconditioner moves no vector; u has halo room because it is what the sharded SpMV multiplies.  Per iteration: one cycle,
+// one sharded SpMV, at most four passes over the local rows and three all-reduces of {sum, failure flag} (two without a
+// preconditioner: rho' = |r|^2 is the sum the update pass already made).  Every decision that changes how many collectives
+// follow — the loop test, a failure — is taken from all-reduced values; breakdown (u.c zero or not finite) is pcg_dev's: alpha
+// and the residual stop being finite, `resid > tol` is false on every rank, the loop ends.
+int amgh_dist_pcg_d(amgh_dist_t* d, const real* b_loc_d, real* x_loc_d, int cycle_, int use_precond, int maxiter, double abstol,
+                    double reltol, real* resid_hist, int* iters) {
+  RC_TRY(dist_check(d));
+  if (cycle_ < 0 || cycle_ > 2 || maxiter < 0) return AMGH_EINVAL;
+  if (d->levels.empty() && d->host_exec) return AMGH_EUNSUPPORTED;   // (host execution is for sharded levels over a host tail)
+  VecPlan& p0 = d->xplan[0];
+  const int64_t n = p0.nloc(), nx = n + p0.nhalo();
+  // from here on nothing returns before the collectives the other ranks wait in: what fails on this rank alone — its pointers
+  // included — raises `fail`, skips this rank's remaining work and travels with the next all-reduce
+  const bool badptr = n > 0 && (!b_loc_d || !x_loc_d);
+  int fail = badptr ? AMGH_EINVAL : AMGH_OK;
+  DPCG_DO(dist_setdev(d));
+  if (d->levels.empty()) {
+    const int rc = dist_pcg_collapsed(d, b_loc_d, x_loc_d, cycle_, use_precond, maxiter, abstol, reltol, resid_hist, iters, fail);
+    return badptr ? AMGH_EINVAL : rc;
+  }
+  DistLevel* L = d->levels[0];
+  DPCG_DO(dist_ensure_pcg_bufs(d));
+  real *r = L->b, *z = L->x, *u = d->pc_u, *c = d->pc_c;
+  DPCG_DO(dist_copy(d, r, b_loc_d, n));
+  DPCG_DO(dist_zero(d, x_loc_d, n));
+  DPCG_DO(dist_zero(d, u, nx));
+  double rr = 0.0;   // |r|^2
+  DPCG_DO(dpcg_local_dot(d, r, r, n, &rr));
+  RC_TRY(dpcg_allreduce(d, &rr, &fail));
+  real resid = std::sqrt((real)rr);
+  const real tol = std::max(reltol * resid, abstol);
+  if (resid_hist && !fail) resid_hist[0] = resid;
+  double rho = 1.0;
+  int it = 0;
+  while (!fail && it < maxiter && resid > tol) {
+    double rho_new = rr;
+    if (use_precond) {
+      DPCG_DO(dist_zero(d, z, nx));
+      DPCG_DO(dist_apply_cycle(d, cycle_, true));                       // z = Pl r, left in the level's x
+      DPCG_DO(dpcg_local_dot(d, z, r, n, &rho_new));
+      RC_TRY(dpcg_allreduce(d, &rho_new, &fail));
+      if (fail) break;
+    }
+    const double beta = (double)((real)rho_new / (real)rho);
+    rho = rho_new;
+    DPCG_DO(dpcg_dir(d, u, use_precond ? z : r, beta, n));             // u = z + beta u
+    DPCG_DO(dist_apply(d, L->A, M_SPMV, p0, u, nullptr, c, 0.0));       // c = A u
+    double uc = 0.0;
+    DPCG_DO(dpcg_local_dot(d, u, c, n, &uc));
+    RC_TRY(dpcg_allreduce(d, &uc, &fail));
+    if (fail) break;
+    const double alpha = (double)((real)rho / (real)uc);
+    DPCG_DO(dpcg_update(d, x_loc_d, u, r, c, alpha, n, &rr));          // x += alpha u, r -= alpha c, |r|^2
+    RC_TRY(dpcg_allreduce(d, &rr, &fail));
+    if (fail) break;
+    resid = std::sqrt((real)rr);
+    ++it;
+    if (resid_hist) resid_hist[it] = resid;
+  }
+  if (!d->host_exec) {
+    DPCG_DO(d->tr->wait_stream(d->stream));
+    DPCG_DO(bw_err_check());   // (the levels sweep by dataflow kernels too: a poll give-up is this call's error)
+  }
+  double f = fail ? 1.0 : 0.0;   // ... on every rank: they return AMGH_ESTATE together
+  RC_TRY(d->tr->allreduce(&f, 1, true));
+  if (iters) *iters = it;
+  if (badptr) return AMGH_EINVAL;
+  return f != 0.0 ? AMGH_ESTATE : AMGH_OK;
+}
+#undef DPCG_DO
 
 // y_loc = A_level x_loc with the halo exchange in front (roofline hook of the sharded SpMV).  Enqueue only.
 int amgh_dist_spmv_d(amgh_dist_t* d, int level, const real* x_loc_d, real* y_loc_d) {

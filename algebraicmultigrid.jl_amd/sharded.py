@@ -362,6 +362,23 @@ class ShardedHierarchy:
         nh = iters.value + 1 if calculate_residual else 1
         return self._down(self._x), hist[:nh].copy()
 
+    def cg(self, b_local, cycle=CYCLE_V, use_precond=True, maxiter=None, abstol=0.0, reltol=None, log=False):
+        """cg(A, b; Pl = aspreconditioner(ml)) over the ranks, x0 = 0 (amgh_dist_pcg_d): IterativeSolvers.jl's recurrence on this
+        rank's rows, every vector resident where the handle executes.  Collective.  use_precond=False: plain CG.  Defaults
+        as `AMG.cg`: maxiter = rows of the whole operator, reltol = sqrt(eps) of the handle's dtype.  Returns x_local, or
+        (x_local, hist) with log=True: hist[k] = the global |r| after k iterations, the same bits on every rank."""
+        if self.plans_only:
+            raise AMGError("cg: a plans-only handle (device < 0 without a host tail) has no data path")
+        maxiter = int(self.cuts[0][-1]) if maxiter is None else int(maxiter)
+        reltol = float(np.sqrt(np.finfo(self.dtype).eps)) if reltol is None else float(reltol)
+        self.set_rhs(b_local)
+        hist = np.zeros(max(maxiter, 0) + 1, dtype=self.dtype)
+        iters = C.c_int(0)
+        hip_check(self.lib.amgh_dist_pcg_d(self.h, self._b.ptr, self._x.ptr, cycle, int(bool(use_precond)), maxiter, float(abstol),
+                                           reltol, hist.ctypes.data, C.byref(iters)), "dist_pcg")
+        x = self._down(self._x)
+        return (x, hist[:iters.value + 1].copy()) if log else x
+
     def spmv(self, level, x_local):
         """y = A_level x on this rank's rows (halo exchange included)."""
         r0, r1 = self.local_range(level)

@@ -468,6 +468,14 @@ int amgh_dist_precond_apply_d(amgh_dist_t* d, const amgh_real* r_loc_d, amgh_rea
 int amgh_dist_solve_d(amgh_dist_t* d, const amgh_real* b_loc_d, amgh_real* x_loc_d, int cycle, int maxiter,
                       double abstol, double reltol, int calculate_residual,
                       amgh_real* resid_hist /*host*/, int* iters);
+/* cg(A, b; Pl, abstol, reltol, maxiter) over the ranks: IterativeSolvers.jl's recurrence as amgh_pcg runs it, on this
+ * rank's rows (device pointers; host pointers on a host-executed handle); x0 = 0; collective.  use_precond = 0: plain CG.
+ * resid_hist: NULL or maxiter + 1 host values ([0] = norm(b), global norms, the same bits on every rank); *iters likewise.
+ * An iteration is one cycle, one sharded SpMV, at most four passes over the local rows and three all-reduces of one sum
+ * each; the vectors never leave the device.  A rank whose local work fails still takes part in the all-reduces (its
+ * failure travels with the sum): every rank then returns AMGH_ESTATE.                                                   */
+int amgh_dist_pcg_d(amgh_dist_t* d, const amgh_real* b_loc_d, amgh_real* x_loc_d, int cycle, int use_precond,
+                    int maxiter, double abstol, double reltol, amgh_real* resid_hist /*host*/, int* iters);
 /* y_loc = A_level x_loc, halo exchange included (roofline hook of the sharded SpMV).  Enqueue only.
  * x_loc_d = NULL multiplies the level's resident x (as the last cycle left it) without a copy.       */
 int amgh_dist_spmv_d(amgh_dist_t* d, int level, const amgh_real* x_loc_d, amgh_real* y_loc_d);

@@ -341,4 +341,16 @@ precond_apply_d!(s::HipSharded, r_d::Ptr{Float64}, z_d::Ptr{Float64}, cycle::Cyc
     check(ccall((:amgh_dist_precond_apply_d, libamghip), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Cint),
                 s.handle, r_d, z_d, cyclecode(cycle)))
 
+# cg(A, b; Pl = aspreconditioner(ml), abstol, reltol, maxiter) over the ranks, x0 = 0, on device pointers (this rank's rows;
+# collective).  Returns (iterations, residual norms): global norms, the same on every rank.  `n` = rows of the whole operator.
+function cg_d!(s::HipSharded, x_d::Ptr{Float64}, b_d::Ptr{Float64}, n::Integer; cycle::Cycle = V(), use_precond::Bool = true,
+               maxiter::Integer = n, abstol::Real = 0.0, reltol::Real = sqrt(eps(Float64)))
+    hist = zeros(Float64, maxiter + 1)
+    iters = Ref{Cint}(0)
+    check(ccall((:amgh_dist_pcg_d, libamghip), Cint,
+                (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Cint, Cint, Cint, Cdouble, Cdouble, Ptr{Float64}, Ref{Cint}),
+                s.handle, b_d, x_d, cyclecode(cycle), use_precond ? 1 : 0, maxiter, abstol, reltol, hist, iters))
+    iters[], hist[1:iters[] + 1]
+end
+
 end # module
