@@ -188,6 +188,14 @@ def _bind_solve_phase(L, creal, coarse_fn):
     L.amgh_debug_bw_dict.argtypes = [vp, C.c_int]
     L.amgh_debug_bw_late.argtypes = [vp, C.c_int]
     L.amgh_debug_coded_ops.argtypes = [vp, C.c_int]
+    L.amgh_debug_set_sell_stream.argtypes = [C.c_int, i64, C.c_int]
+    L.amgh_debug_sell_stream_launches.argtypes = [vp, C.c_int, C.c_int]
+    L.amgh_debug_sell_stream_padded.argtypes = [vp, C.c_int, C.c_int]
+    L.amgh_debug_sell_stream_padded.restype = i64
+    L.amgh_debug_csr_sell.argtypes = [vp, C.c_int]
+    L.amgh_debug_csr_sell.restype = i64
+    L.amgh_debug_csr_sell_launches.argtypes = [vp]
+    L.amgh_debug_csr_sell_apply.argtypes = [vp, C.c_int, vp, vp, vp]
     L.amgh_debug_bw_sweep_host.argtypes = [i64, vp, vp, vp, C.c_int, C.c_int, C.c_double, vp, vp, vp]
     L.amgh_debug_bw_dict_sweep_host.argtypes = [i64, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp]
     L.amgh_debug_set_tunable.argtypes = [C.c_char_p, C.c_int]

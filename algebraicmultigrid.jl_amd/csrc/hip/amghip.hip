@@ -39,6 +39,7 @@ struct Level {
   amgh_csr Pp, Rp;
   bool lo_ok = false;
   real* lo_val = nullptr;  // S != A with the same pattern: values of A in the order of the schedule's level-ordered copy of S
+  SellCols lo_sc;          // sliced-ELL copy of the level-ordered A (single-column hierarchies, big levels: sell_build)
   CodedCols lo_cc;         // value-coded columns of the level-ordered A (the schedule's copy with lo_val or its own values)
   // blocks of right-hand sides: restriction / prolongation of this level column by column through the stream kernel instead of
   // the interleaved copy (chosen by a timing at amgh_finalize where the operator has value-coded columns: bitwise the same sums)
@@ -321,14 +322,14 @@ int cycle(amgh_t* h, int l, real* x, const real* b, int cyc, bool xzero, bool lo
         RC_TRY(resid_cols(bs, g->rowptr, g->col, L->lo_val ? L->lo_val : g->val, n, g->xp, xs, g->bp, n, L->res, n, h->stream, &L->lo_cc));
       else
         RC_TRY(raw_apply(M_RESID, g->rowptr, g->col, L->lo_val ? L->lo_val : g->val, n, g->xp, xs, g->bp, n, L->res, n,
-                         h->stream, bs, &L->lo_cc));
+                         h->stream, bs, &L->lo_cc, &L->lo_sc));
     }
     {
       ProfScope p(h, AMGH_T_RESTRICT, l);
       if (L->il && il_block(bs) && !(L->r_stream && g_rhs_il == 1))
         RC_TRY(il_apply(bs, false, L->Rp.rowptr, L->Rp.col, L->Rp.val, nc, L->res, n, n, L->il, C ? cg->bp : L->cb, nc, h->stream, &L->Rp.cc));
       else
-        RC_TRY(csr_apply(&L->Rp, M_SPMV, L->res, nullptr, C ? cg->bp : L->cb, h->stream, bs));
+        RC_TRY(csr_apply(&L->Rp, M_SPMV, L->res, nullptr, C ? cg->bp : L->cb, h->stream, bs, true));
       if (C) cg->bp_cols = bs;          // the next level's level-ordered right-hand side is in place
     }
     if (!C) RC_TRY(vec_fill(h, L->cx, nc * bs, 0.0));
@@ -349,7 +350,7 @@ int cycle(amgh_t* h, int l, real* x, const real* b, int cyc, bool xzero, bool lo
                         g->xp, xs, h->stream, &L->Pp.cc));
       else
         RC_TRY(raw_apply(M_ADD, L->Pp.rowptr, L->Pp.col, L->Pp.val, n, C ? cg->xp : L->cx, C ? cg->xstride : nc, nullptr, 0, g->xp,
-                         xs, h->stream, bs, &L->Pp.cc));
+                         xs, h->stream, bs, &L->Pp.cc, &L->Pp.sc));
     }
     {
       ProfScope p(h, AMGH_T_POSTSMOOTH, l);
@@ -359,14 +360,14 @@ int cycle(amgh_t* h, int l, real* x, const real* b, int cyc, bool xzero, bool lo
   }
   {
     ProfScope p(h, AMGH_T_RESIDUAL, l);
-    RC_TRY(csr_apply(&L->A, M_RESID, xc, b, L->res, h->stream, bs));
+    RC_TRY(csr_apply(&L->A, M_RESID, xc, b, L->res, h->stream, bs, true));
   }
   {
     ProfScope p(h, AMGH_T_RESTRICT, l);
     if (L->il && il_block(bs))
       RC_TRY(il_apply(bs, false, L->R.rowptr, L->R.col, L->R.val, nc, L->res, n, n, L->il, L->cb, nc, h->stream));
     else
-      RC_TRY(csr_apply(&L->R, M_SPMV, L->res, nullptr, L->cb, h->stream, bs));
+      RC_TRY(csr_apply(&L->R, M_SPMV, L->res, nullptr, L->cb, h->stream, bs, true));
   }
   RC_TRY(vec_fill(h, L->cx, nc * bs, 0.0));
   if (l == (int)h->levels.size() - 1) {
@@ -383,7 +384,7 @@ int cycle(amgh_t* h, int l, real* x, const real* b, int cyc, bool xzero, bool lo
     if (L->il && il_block(bs))
       RC_TRY(il_apply(bs, true, L->P.rowptr, L->P.col, L->P.val, n, L->cx, nc, nc, L->il, xc, n, h->stream));
     else
-      RC_TRY(csr_apply(&L->P, M_ADD, L->cx, nullptr, xc, h->stream, bs));
+      RC_TRY(csr_apply(&L->P, M_ADD, L->cx, nullptr, xc, h->stream, bs, true));
   }
   {
     ProfScope p(h, AMGH_T_POSTSMOOTH, l);
@@ -930,6 +931,7 @@ void amgh_destroy(amgh_t* h) {
     csr_free(&L->A); csr_free(&L->S); csr_free(&L->P); csr_free(&L->R); csr_free(&L->Pp); csr_free(&L->Rp);
     hipFree(L->res); hipFree(L->cx); hipFree(L->cb); hipFree(L->tmp); hipFree(L->cheb_d); hipFree(L->lo_val); hipFree(L->il);
     L->lo_cc.free_dev();
+    L->lo_sc.free_dev();
     delete L;
   }
   csr_free(&h->finalA);
@@ -953,6 +955,7 @@ static void level_discard(Level* L) {
   csr_free(&L->A); csr_free(&L->S); csr_free(&L->P); csr_free(&L->R); csr_free(&L->Pp); csr_free(&L->Rp);
   hipFree(L->lo_val);
   L->lo_cc.free_dev();
+  L->lo_sc.free_dev();
   delete L;
 }
 
@@ -1491,6 +1494,69 @@ int amgh_finalize(amgh_t* h) {
       L->Rp.xcd_map = ms[1] < 0.93 * ms[0];
       if (getenv("AMGH_VERBOSE")) fprintf(stderr, "[amghip] n=%lld restriction: %.3f ms, XCD-contiguous %.3f ms -> %s\n", (long long)L->n, ms[0] / 4, ms[1] / 4, L->Rp.xcd_map ? "XCD-contiguous" : "plain");
     }
+  // Sliced-ELL copies of the same operators for the single-column cycle (sell_build: big operators whose padding stays under the cap;
+  // from the coded words where they exist, else from columns and values), after the timings above: those are csr_stream_kernel's.
+  if (h->nrhs == 1)
+    for (Level* L : h->levels) {
+      GsSchedule* g = L->smat()->gs;
+      const bool cd = g_stream_code != 0;
+      if (!(L->lo_ok && g && g->nblk == 0)) {
+        // a level whose cycle runs in natural order (cycle()'s second branch): its A, R, P themselves, where the hierarchy holds them
+        for (amgh_csr* M : {&L->A, &L->R, &L->P})
+          if (M->rowptr) { RC_TRY(sell_build(M->rowptr, cd ? M->cc.ccol : nullptr, M->col, M->val, M->nrows, M->nnz, &M->sc, h->stream)); ws += M->sc.bytes; }
+        continue;
+      }
+      if (!g->rowptr || g->compacted) continue;
+      RC_TRY(sell_build(g->rowptr, cd ? L->lo_cc.ccol : nullptr, g->col, L->lo_val ? L->lo_val : g->val, L->n, g->nnz, &L->lo_sc, h->stream));
+      RC_TRY(sell_build(L->Rp.rowptr, cd ? L->Rp.cc.ccol : nullptr, L->Rp.col, L->Rp.val, L->Rp.nrows, L->Rp.nnz, &L->Rp.sc, h->stream));
+      RC_TRY(sell_build(L->Pp.rowptr, cd ? L->Pp.cc.ccol : nullptr, L->Pp.col, L->Pp.val, L->Pp.nrows, L->Pp.nnz, &L->Pp.sc, h->stream));
+      // Passing the structural rule is not yet winning (the fine restriction ties in the cycle; a restriction may have the XCD-contiguous CSR
+      // launch picked above): as for xcd_map, every copy of a big operator is timed against the CSR launch it would replace, in the mode
+      // the cycle uses, on the level's own buffers, and stays only where it is at least 3 % faster.  Both paths give the same bits, so the
+      // choice cannot change results.  (With the row threshold lowered through amgh_debug_set_sell_stream — tests — the rule alone decides:
+      // which operators have a copy is then a function of the matrices.)
+      if (L->n >= (1 << 18) && g_sell_min_rows >= ((int64_t)1 << 18)) {
+        real* ty = nullptr;
+        RC_TRY(dev_alloc(&ty, L->n));
+        int rc = AMGH_OK;
+        if (hipMemsetAsync(ty, 0, sizeof(real) * L->n, h->stream) != hipSuccess || hipMemsetAsync(L->res, 0, sizeof(real) * L->n, h->stream) != hipSuccess ||
+            hipMemsetAsync(L->cx, 0, sizeof(real) * L->nc, h->stream) != hipSuccess) rc = -1001;
+        const real* val = L->lo_val ? L->lo_val : g->val;
+        auto run = [&](int which) -> int {
+          if (which == AMGH_OP_A) return raw_apply(M_RESID, g->rowptr, g->col, val, L->n, L->res, L->n, L->res, L->n, ty, L->n, h->stream, 1, &L->lo_cc, &L->lo_sc);
+          if (which == AMGH_OP_R) return csr_apply(&L->Rp, M_SPMV, L->res, nullptr, L->cb, h->stream, 1, true);
+          return raw_apply(M_ADD, L->Pp.rowptr, L->Pp.col, L->Pp.val, L->n, L->cx, L->nc, nullptr, 0, ty, L->n, h->stream, 1, &L->Pp.cc, &L->Pp.sc);
+        };
+        const int keep = g_sell_stream;
+        for (int which : {AMGH_OP_A, AMGH_OP_R, AMGH_OP_P}) {
+          SellCols* sc = which == AMGH_OP_A ? &L->lo_sc : which == AMGH_OP_R ? &L->Rp.sc : &L->Pp.sc;
+          if (!sc->w || (which == AMGH_OP_R ? L->Rp.nrows : L->n) < (1 << 18)) continue;
+          double ms[2] = {0, 0};
+          for (int v = 0; v < 2 && rc == AMGH_OK; ++v) {
+            g_sell_stream = v;
+            rc = run(which);
+            if (rc == AMGH_OK && hipEventRecord(h->t0, h->stream) != hipSuccess) rc = -1001;
+            for (int r = 0; r < 4 && rc == AMGH_OK; ++r) rc = run(which);
+            float t = 0.f;
+            if (rc == AMGH_OK && (hipEventRecord(h->t1, h->stream) != hipSuccess || hipEventSynchronize(h->t1) != hipSuccess ||
+                                  hipEventElapsedTime(&t, h->t0, h->t1) != hipSuccess)) rc = -1001;
+            ms[v] = t;
+          }
+          sc->launches = 0;
+          if (rc != AMGH_OK) break;
+          if (getenv("AMGH_VERBOSE")) fprintf(stderr, "[amghip] n=%lld operator %d: csr_stream_kernel %.3f ms, sliced-ELL %.3f ms\n", (long long)L->n, which, ms[0] / 4, ms[1] / 4);
+          if (!(ms[1] < 0.97 * ms[0])) sc->free_dev();
+        }
+        g_sell_stream = keep;
+        if (hipStreamSynchronize(h->stream) != hipSuccess && rc == AMGH_OK) rc = -1001;
+        hipFree(ty);
+        RC_TRY(rc);
+      }
+      ws += L->lo_sc.bytes + L->Rp.sc.bytes + L->Pp.sc.bytes;
+      if (getenv("AMGH_VERBOSE"))
+        fprintf(stderr, "[amghip] n=%lld sliced-ELL padded / entries: A %.3f  R %.3f  P %.3f (0: not taken)\n", (long long)L->n, (double)L->lo_sc.padded / std::max<int64_t>(1, g->nnz),
+                (double)L->Rp.sc.padded / std::max<int64_t>(1, L->Rp.nnz), (double)L->Pp.sc.padded / std::max<int64_t>(1, L->Pp.nnz));
+    }
   // Trimmed footprint (the default): where an operator the level-ordered cycle streams has value-coded columns, the cycle reads
   // THEM — 4 bytes per entry — and the 12 bytes of columns and values beside them are a copy nothing in it touches: released
   // (the restriction and prolongation of the level; its A where the level sweeps the block layout as a dataflow alone, so that
@@ -1898,6 +1964,7 @@ struct LoOp {
   int64_t nrows = 0, ncols = 0;
   const int32_t *row_perm = nullptr, *col_perm = nullptr;
   const CodedCols* cc = nullptr;   // value-coded columns of the same operator (the trimmed footprint keeps only them: col / val nullptr)
+  const SellCols* sc = nullptr;    // its sliced-ELL copy (what the cycle's own launches read where it was built)
 };
 static bool level_lo_op(amgh_t* h, int level, int which, LoOp* o) {
   if (level < 0 || level >= (int)h->levels.size()) return false;
@@ -1914,13 +1981,13 @@ static bool level_lo_op(amgh_t* h, int level, int which, LoOp* o) {
   switch (which) {
     case AMGH_OP_A:
       if ((int64_t)g->ncols != L->n) return false;
-      *o = LoOp{g->rowptr, g->col, L->lo_val ? L->lo_val : g->val, L->n, L->n, g->perm, g->perm, &L->lo_cc};
+      *o = LoOp{g->rowptr, g->col, L->lo_val ? L->lo_val : g->val, L->n, L->n, g->perm, g->perm, &L->lo_cc, &L->lo_sc};
       return g->rowptr != nullptr && !g->compacted;
     case AMGH_OP_P:
-      *o = LoOp{L->Pp.rowptr, L->Pp.col, L->Pp.val, L->n, L->nc, g->perm, coarse_perm, &L->Pp.cc};
+      *o = LoOp{L->Pp.rowptr, L->Pp.col, L->Pp.val, L->n, L->nc, g->perm, coarse_perm, &L->Pp.cc, &L->Pp.sc};
       return L->Pp.rowptr != nullptr;
     case AMGH_OP_R:
-      *o = LoOp{L->Rp.rowptr, L->Rp.col, L->Rp.val, L->nc, L->n, coarse_perm, g->perm, &L->Rp.cc};
+      *o = LoOp{L->Rp.rowptr, L->Rp.col, L->Rp.val, L->nc, L->n, coarse_perm, g->perm, &L->Rp.cc, &L->Rp.sc};
       return L->Rp.rowptr != nullptr;
   }
   return false;
@@ -2236,7 +2303,8 @@ int amgh_bench_op(amgh_t* h, int level, int which, int reps, int warmup, double*
     }
     const int mode = (which == 3 || which == 5) ? M_RESID : M_SPMV;
     if (op) return csr_apply(op, mode, x, b, y, h->stream);
-    return raw_apply(mode, lo.rowptr, lo.col, lo.val, lo.nrows, x, lo.ncols, b, lo.nrows, y, lo.nrows, h->stream, 1, lo.cc);
+    // (5 / 6 / 7: as the cycle launches them, the sliced-ELL copy included; 0 - 3 stay on csr_stream_kernel)
+    return raw_apply(mode, lo.rowptr, lo.col, lo.val, lo.nrows, x, lo.ncols, b, lo.nrows, y, lo.nrows, h->stream, 1, lo.cc, which >= 5 ? lo.sc : nullptr);
     if (which == 4) {
       if (level >= (int)h->levels.size()) return AMGH_EINVAL;
       return level_smooth_enqueue(h, level, 0, y, b);
@@ -2606,6 +2674,58 @@ int amgh_debug_get_perm_io(void) { return g_gs_flow_perm_io; }
 // Sweeps launched so far with b read through the permutation (which = 0) / with x written in natural order too (1): what a test
 // reads before and after a call to know that the call ran them (a captured cycle counts when it is captured, not when replayed).
 int amgh_debug_perm_io_sweeps(int which) { return (which == 0 || which == 1) ? (int)(g_perm_io_sweeps[which] & 0x7fffffffu) : -1; }
+
+// The switch of the sliced-ELL launches (sell_apply, csr_ops.hpp): `on` is read at every launch, `min_rows` and `cap_pct` at
+// amgh_finalize (min_rows <= 0 / cap_pct <= 0: the compiled-in 2^18 rows / kSellCapPct, kSellCapPlainPct).
+int amgh_debug_set_sell_stream(int on, int64_t min_rows, int cap_pct) {
+  g_sell_stream = on != 0;
+  g_sell_min_rows = min_rows > 0 ? min_rows : (int64_t)1 << 18;
+  g_sell_cap_pct = cap_pct > 0 ? cap_pct : 0;
+  ++g_sched_epoch;   // captured cycles bake the execution path in
+  return AMGH_OK;
+}
+int amgh_debug_get_sell_stream(void) { return g_sell_stream; }
+static const SellCols* sell_of(const amgh_t* h, int level, int which) {
+  if (!h || level < 0 || level >= (int)h->levels.size()) return nullptr;
+  const Level* L = h->levels[level];
+  const GsSchedule* g = (L->has_S ? L->S : L->A).gs;
+  if (!(L->lo_ok && g && g->nblk == 0))   // (the level's cycle runs in natural order: the operators themselves)
+    return which == AMGH_OP_A ? &L->A.sc : which == AMGH_OP_R ? &L->R.sc : which == AMGH_OP_P ? &L->P.sc : nullptr;
+  return which == AMGH_OP_A ? &L->lo_sc : which == AMGH_OP_R ? &L->Rp.sc : which == AMGH_OP_P ? &L->Pp.sc : nullptr;
+}
+int amgh_debug_sell_stream_launches(const amgh_t* h, int level, int which) {
+  const SellCols* sc = sell_of(h, level, which);
+  return sc ? (int)(sc->launches & 0x7fffffffu) : -1;
+}
+int64_t amgh_debug_sell_stream_padded(const amgh_t* h, int level, int which) {
+  const SellCols* sc = sell_of(h, level, which);
+  return sc ? (sc->w ? sc->padded : 0) : -1;
+}
+
+// A stand-alone operator's own sliced-ELL copy (tests of the layout: amgh_debug_csr_sell_apply then launches through it
+// while the switch is on): from value-coded words where `coded` and the operator has at most 256 distinct values, else from its
+// columns and values; the row threshold and the cap are amgh_debug_set_sell_stream's.  Returns the padded entries, 0 where the
+// operator does not take the layout.
+int64_t amgh_debug_csr_sell(amgh_csr_t* op, int coded) {
+  if (!op) return AMGH_EINVAL;
+  HIP_TRY(hipSetDevice(op->device));
+  if (coded && !op->cc.ccol) {
+    RC_TRY(code_values(op->col, op->val, op->nrows, op->ncols, op->nnz, &op->cc, nullptr, 1));
+    op->bytes += op->cc.bytes;
+  }
+  RC_TRY(sell_build(op->rowptr, coded ? op->cc.ccol : nullptr, op->col, op->val, op->nrows, op->nnz, &op->sc, nullptr));
+  op->bytes += op->sc.bytes;
+  return op->sc.w ? op->sc.padded : 0;
+}
+// y = op x (mode 0), y = b - op x (1), y = y + op x (2) as the cycle launches an operator that has a copy: through it while the switch is on
+int amgh_debug_csr_sell_apply(amgh_csr_t* op, int mode, const real* x_d, const real* b_d, real* y_d) {
+  if (!op || !x_d || !y_d || mode < M_SPMV || mode > M_ADD || (mode == M_RESID && !b_d)) return AMGH_EINVAL;
+  HIP_TRY(hipSetDevice(op->device));
+  RC_TRY(csr_apply(op, mode, x_d, b_d, y_d, nullptr, 1, true));
+  HIP_TRY(hipDeviceSynchronize());
+  return AMGH_OK;
+}
+int amgh_debug_csr_sell_launches(const amgh_csr_t* op) { return op ? (int)(op->sc.launches & 0x7fffffffu) : -1; }
 
 int amgh_debug_chain_timing(int enable, unsigned long long* out8) {
   if (enable && !g_chain_tim) {

@@ -370,8 +370,25 @@ struct CodedCols {
   void free_dev() { hipFree(ccol); hipFree(vtab); ccol = nullptr; vtab = nullptr; n = 0; bytes = 0; }
 };
 
+// Sliced-ELL copy of an operator the level-ordered cycle streams (sell_stream_kernel; built by sell_build, csr_ops.hpp, at
+// amgh_finalize): slices of 64 consecutive rows in the operator's own order, entry t of row 64 s + lane at 64 (off[s] + t) + lane.
+// Coded form (v == nullptr): w holds the CodedCols words and the launches read that operator's vtab; plain form: w the columns,
+// v the values.  len8: the rows' lengths as bytes (nullptr where a row is longer than 255: the kernel then takes them from rowptr).
+// Padded entries / entries, in percent, up to which the padded layout is taken (256^3, profiles/r09_sell_stream.log).  Coded words: the
+// prolongation of 8.4 M rows at 127 % runs in 0.85 of csr_stream_kernel's time, the one of 1.4 M rows at 134 % in 1.03, the fine
+// one at 172 % in 1.26.  Plain columns + values pay 12 bytes per padded entry: 127 % already loses (1.08); everything at <= 102 % wins.
+constexpr int kSellCapPct = 130, kSellCapPlainPct = 110;
+constexpr int kSellLongSteps = 12;   // coded slices that average this many steps take 8 entries per round (sell_apply)
+struct SellCols {
+  uint32_t* w = nullptr; real* v = nullptr; uint2* slice = nullptr; uint8_t* len8 = nullptr;
+  int64_t nslices = 0, padded = 0, bytes = 0;
+  unsigned launches = 0;   // launches that went through sell_stream_kernel (amgh_debug_sell_stream_launches)
+  void free_dev() { hipFree(w); hipFree(v); hipFree(slice); hipFree(len8); w = nullptr; v = nullptr; slice = nullptr; len8 = nullptr; nslices = padded = bytes = 0; }
+};
+
 struct amgh_csr {
   CodedCols cc;
+  SellCols sc;            // (the level-ordered restriction / prolongation of big single-column levels)
   bool cc_tried = false;  // csr_ensure_coded has looked at this operator (natural-order operators of Chebyshev smoothers)
   bool xcd_map = false;   // SpMV launches of this operator with the XCD-contiguous mapping of the workgroups (amgh_finalize times both)
   int device = 0;
@@ -417,6 +434,9 @@ int g_gs_bw_dict = 1;           // the relayed single-column sweep reads the dic
 int g_gs_bw_relay = 3;          // walker waves a single-column dataflow sweep relays a block's walk between (gs_relay.hpp: the one instantiated count, BW_RELAY_W; 0: one walker, gs_bw_flow_kernel — bitwise the same); read at every sweep
 int g_gs_flow_xzero = 1;        // a dataflow sweep that starts a smooth! call on x = 0 reads no x (0: fill + read as any other sweep — bitwise the same); read at every sweep
 int g_gs_flow_perm_io = 1;      // the relayed sweep that starts / ends a single-column smooth! call reads b through the permutation / writes x in natural order too (0: gather_perm_kernel and scatter_perm_kernel — bitwise the same); amgh_debug_set_perm_io, read at every sweep
+int g_sell_stream = 1;          // the residual / restriction / prolongation launches of the level-ordered single-column cycle go through the sliced-ELL copy of their operator where one was built (sell_stream_kernel; 0: csr_stream_kernel — bitwise the same); amgh_debug_set_sell_stream, read at every launch
+int64_t g_sell_min_rows = (int64_t)1 << 18;   // ... built at amgh_finalize for operators of at least this many rows
+int g_sell_cap_pct = 0;                       // ... whose padded entries are at most this many percent of their entries (0: kSellCapPct / kSellCapPlainPct by form)
 unsigned int g_perm_io_sweeps[2] = {0, 0};  // sweeps launched with b read through the permutation / with x written in natural order too (amgh_debug_perm_io_sweeps: what a test asks to know that a case ran them)
 int g_gs_bw_two_min_rows = 200000;  // wavefront of blocks: operators with TWO offset classes (2-D grids) take it from this many rows where the cost model agrees (0 = never); round 4: 6 000 000; with the relayed dataflow sweep 512^2 / 1024^2 / 2048^2 Poisson V-cycles 4.82 -> 3.92 / 9.35 -> 8.50 / 21.6 -> 18.3 ms, 4096^2 39.1 -> 39.9 (profiles/r05_block_layout_threshold.log); read at schedule build
 int g_gs_sell = 1;              // merged groups from the SELL-like layout where it was built (0 = slot kernels); build: read at schedule build too
@@ -475,6 +495,7 @@ void csr_free(amgh_csr* op) {
   hipFree(op->rowptr); hipFree(op->col); hipFree(op->val);
   hipFree(op->dpos); hipFree(op->diag);
   op->cc.free_dev();
+  op->sc.free_dev();
   if (op->gs) { op->gs->free_dev(); delete op->gs; }
   op->rowptr = op->col = op->dpos = nullptr; op->val = op->diag = nullptr; op->gs = nullptr;
 }

@@ -338,6 +338,109 @@ __global__ __launch_bounds__(CFG::THREADS) void csr_stream_kernel(StreamArgs a) 
 // default configuration used by the library (tools/spmv_bench.hip, profiles/r01_spmv_variants.log)
 using DefaultCfg = StreamCfg<1024, 1024, 8192, 4, false, false>;
 
+// ---- SpMV-type passes from a sliced-ELL copy (SellCols): one row per lane ------------------------------------------------
+// csr_stream_kernel loads entries in CSR order: one x gather instruction holds 64 entries of ~64 / (row length) consecutive
+// rows, i.e. different stencil offsets of a few rows, and its addresses fall into nearly as many 64-byte segments as there are
+// lanes.  Here a slice is 64 consecutive rows (the operator's own order, nothing is renumbered) and entry t of row 64 s + lane
+// sits at 64 (off[s] + t) + lane: a gather instruction holds entry position t of 64 consecutive rows (on a lattice the same
+// stencil offset: a few contiguous runs of x), the matrix words of a step are one coalesced line per wave, the products never
+// pass LDS and there is no barrier behind the table load.  A lane knows its row's length and stops there (t < len: no
+// sentinel — every 32-bit word is a legal coded entry); acc starts at 0.0 and takes acc + v * x[c] in CSR entry order with
+// the product rounded on its own, and the epilogue is csr_stream_kernel's: the same bits.
+struct SellStreamArgs {
+  const uint32_t* w;       // padded entries, slice after slice: the coded word (col | code << 24) or the plain column
+  const real* v;           // plain form: the values, same indexing (coded form: nullptr)
+  const uint2* slice;      // per slice {offset in units of 64 entries, steps}
+  const uint8_t* len;      // per row: its length (nullptr where a row is longer than 255: then from rowptr)
+  const int32_t* rowptr;
+  const real* vtab;        // coded form: the operator's value table
+  int32_t vtab_n;
+  int32_t nrows, nslices;
+  const real* x;
+  const real* b;           // M_RESID
+  real* y;
+};
+// B: entries of a lane per round; the next round's words are requested before this round's gathers (per lane the products are
+// added in entry order whatever B is)
+template <int MODE, bool CODED, int B>
+__global__ __launch_bounds__(kThreads) void sell_stream_kernel(SellStreamArgs a) {
+  static_assert(MODE == M_SPMV || MODE == M_RESID || MODE == M_ADD, "SpMV-type passes only");
+  __shared__ real s_tab[CODED ? kCodeMax : 1];
+  if (CODED) {
+    if ((int)threadIdx.x < a.vtab_n) s_tab[threadIdx.x] = a.vtab[threadIdx.x];
+    __syncthreads();
+  }
+  const int s = (int)blockIdx.x * (kThreads / kWave) + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  if (s >= a.nslices) return;
+  const int lane = threadIdx.x & (kWave - 1);
+  const int r = s * kWave + lane;
+  const bool live = r < a.nrows;
+  int len = 0;
+  if (live) len = a.len ? (int)a.len[r] : a.rowptr[r + 1] - a.rowptr[r];
+  const uint2 sd = a.slice[s];
+  const int nit = (int)sd.y;   // (uniform over the wave; >= every len of the slice)
+  const int64_t base = (int64_t)sd.x * kWave + lane;
+  uint32_t w[B];
+  real v[B];
+#pragma unroll
+  for (int e = 0; e < B; ++e) {
+    w[e] = 0; v[e] = 0.0;
+    if (e < nit) { w[e] = a.w[base + (int64_t)e * kWave]; if (!CODED) v[e] = a.v[base + (int64_t)e * kWave]; }
+  }
+  real acc = 0.0;
+  for (int t = 0; t < nit; t += B) {
+    uint32_t wn[B];
+    real vn[B];
+#pragma unroll
+    for (int e = 0; e < B; ++e) {
+      wn[e] = 0; vn[e] = 0.0;
+      if (t + B + e < nit) { wn[e] = a.w[base + (int64_t)(t + B + e) * kWave]; if (!CODED) vn[e] = a.v[base + (int64_t)(t + B + e) * kWave]; }
+    }
+    real xv[B];
+#pragma unroll
+    for (int e = 0; e < B; ++e) {
+      const uint32_t c = CODED ? (w[e] & ((1u << kCodeBits) - 1)) : w[e];
+      xv[e] = t + e < len ? a.x[c] : (real)0.0;
+      if (CODED) v[e] = s_tab[w[e] >> kCodeBits];
+    }
+#pragma unroll
+    for (int e = 0; e < B; ++e)
+      if (t + e < len) acc = acc + v[e] * xv[e];
+#pragma unroll
+    for (int e = 0; e < B; ++e) { w[e] = wn[e]; v[e] = vn[e]; }
+  }
+  if (!live) return;
+  if (MODE == M_SPMV) a.y[r] = acc;
+  else if (MODE == M_RESID) a.y[r] = a.b[r] - acc;
+  else a.y[r] = a.y[r] + acc;
+}
+// steps of every slice: its longest row (one thread per slice; the layout is built once per operator)
+__global__ void sell_steps_kernel(const int32_t* rowptr, int nrows, int nslices, int32_t* steps) {
+  const int s = blockIdx.x * blockDim.x + threadIdx.x;
+  if (s >= nslices) return;
+  const int r1 = min(s * kWave + kWave, nrows);
+  int m = 0;
+  for (int r = s * kWave; r < r1; ++r) m = max(m, rowptr[r + 1] - rowptr[r]);
+  steps[s] = m;
+}
+// the rows of the CSR into the padded arrays, one thread per (slice, lane); w_in: coded words or plain columns.  Padding is
+// zero-filled (never gathered: a lane stops at its row's length).
+__global__ void sell_stream_fill_kernel(const int32_t* rowptr, const uint32_t* w_in, const real* v_in, const uint2* slice, int nrows,
+                                        int nslices, uint32_t* w, real* v, uint8_t* len8) {
+  const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int s = (int)(gid >> 6), lane = (int)(gid & 63);
+  if (s >= nslices) return;
+  const uint2 sd = slice[s];
+  const int r = s * kWave + lane;
+  int32_t a0 = 0, len = 0;
+  if (r < nrows) { a0 = rowptr[r]; len = rowptr[r + 1] - a0; if (len8) len8[r] = (uint8_t)len; }
+  const int64_t base = (int64_t)sd.x * kWave + lane;
+  for (int t = 0; t < (int)sd.y; ++t) {
+    w[base + (int64_t)t * kWave] = t < len ? w_in[a0 + t] : 0u;
+    if (v) v[base + (int64_t)t * kWave] = t < len ? v_in[a0 + t] : (real)0.0;
+  }
+}
+
 // In-order sum of s[lo..hi) (plain, un-skewed LDS indices): batches of 8 LDS reads with immediate
 // offsets from one base address, the next batch in flight while the current one is added — the
 // additions themselves stay one strictly sequential chain (the reference's order).

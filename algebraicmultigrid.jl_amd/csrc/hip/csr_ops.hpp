@@ -107,9 +107,11 @@ __global__ void code_encode_kernel(const int32_t* col, const real* val, int64_t 
     ccol[k] = (uint32_t)col[k] | ((uint32_t)code_find(s_tab, ntab, real_bits(val[k])) << kCodeBits);
 }
 // out: the coded columns of (col, val), or left empty where the operator does not qualify (more than 256 distinct values —
-// by bit pattern —, 2^24 columns or more, nothing to gain below 2^18 rows).  A few passes over val on the device.
-int code_values(const int32_t* col, const real* val, int64_t nrows, int64_t ncols, int64_t nnz, CodedCols* out, hipStream_t st) {
-  if (!g_stream_code || out->ccol || nrows < (1 << 18) || ncols > ((int64_t)1 << kCodeBits) || nnz <= 0 || !col || !val) return AMGH_OK;
+// by bit pattern —, 2^24 columns or more, nothing to gain below min_rows = 2^18 rows; amgh_debug_csr_sell codes a small stand-alone
+// operator for the tests of the layout).  A few passes over val on the device.
+int code_values(const int32_t* col, const real* val, int64_t nrows, int64_t ncols, int64_t nnz, CodedCols* out, hipStream_t st,
+                int64_t min_rows = (int64_t)1 << 18) {
+  if (!g_stream_code || out->ccol || nrows < min_rows || ncols > ((int64_t)1 << kCodeBits) || nnz <= 0 || !col || !val) return AMGH_OK;
   unsigned* d_cnt = nullptr; real *d_miss = nullptr, *d_tab = nullptr;
   RC_TRY(dev_alloc(&d_cnt, 1));
   int rc = dev_alloc(&d_miss, kCodeMiss);
@@ -159,15 +161,88 @@ int code_values(const int32_t* col, const real* val, int64_t nrows, int64_t ncol
   return rc;
 }
 
+// ---- sliced-ELL copies (SellCols) ---------------------------------------------------------------------------------------
+// out: the sliced-ELL copy of the operator (rowptr; coded words ccol, or columns col and values val), or left empty where the
+// operator does not qualify: fewer than g_sell_min_rows rows, or padded entries above g_sell_cap_pct percent of its entries (the
+// structural rule: a slice has as many steps as its longest row, so ragged operators — the fine prolongation, rows of 1 and of
+// 6 entries in turn — would read more than csr_stream_kernel does).  One pass over the arrays on the device; the slice
+// descriptors are summed on the host (one int per 64 rows).
+int sell_build(const int32_t* rowptr, const uint32_t* ccol, const int32_t* col, const real* val, int64_t nrows, int64_t nnz,
+               SellCols* out, hipStream_t st) {
+  if (out->w || nrows < g_sell_min_rows || nrows <= 0 || nnz <= 0 || !rowptr || (!ccol && !(col && val))) return AMGH_OK;
+  const int64_t ns = (nrows + kWave - 1) / kWave;
+  int32_t* d_steps = nullptr;
+  RC_TRY(dev_alloc(&d_steps, ns));
+  hipLaunchKernelGGL(sell_steps_kernel, dim3((unsigned)((ns + 255) / 256)), dim3(256), 0, st, rowptr, (int)nrows, (int)ns, d_steps);
+  std::vector<int32_t> steps((size_t)ns);
+  if (hipMemcpyAsync(steps.data(), d_steps, sizeof(int32_t) * ns, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) { hipFree(d_steps); return -1001; }
+  hipFree(d_steps);
+  std::vector<uint2> sd((size_t)ns);
+  int64_t off = 0;
+  int longest = 0;
+  for (int64_t s = 0; s < ns; ++s) { sd[(size_t)s] = make_uint2((unsigned)off, (unsigned)steps[(size_t)s]); off += steps[(size_t)s]; longest = std::max(longest, steps[(size_t)s]); }
+  const int64_t padded = off * kWave;
+  const bool coded = ccol != nullptr;
+  if (off >= ((int64_t)1 << 32) || padded * 100 > nnz * (int64_t)(g_sell_cap_pct > 0 ? g_sell_cap_pct : coded ? kSellCapPct : kSellCapPlainPct)) return AMGH_OK;
+  int rc = dev_alloc(&out->w, padded);
+  if (rc == AMGH_OK && !coded) rc = dev_alloc(&out->v, padded);
+  if (rc == AMGH_OK) rc = dev_alloc(&out->slice, ns);
+  if (rc == AMGH_OK && longest <= 255) rc = dev_alloc(&out->len8, nrows);
+  if (rc == AMGH_OK && hipMemcpyAsync(out->slice, sd.data(), sizeof(uint2) * ns, hipMemcpyHostToDevice, st) != hipSuccess) rc = -1001;
+  if (rc == AMGH_OK) {
+    hipLaunchKernelGGL(sell_stream_fill_kernel, dim3((unsigned)((ns * kWave + 255) / 256)), dim3(256), 0, st, rowptr,
+                       coded ? ccol : (const uint32_t*)col, coded ? (const real*)nullptr : val, (const uint2*)out->slice, (int)nrows, (int)ns,
+                       out->w, out->v, out->len8);
+    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) rc = -1001;   // (sd goes out of scope)
+  }
+  if (rc != AMGH_OK) { out->free_dev(); if (rc == AMGH_ENOMEM) { (void)hipGetLastError(); return AMGH_OK; } return rc; }   // (out of memory: the CSR copy stays)
+  out->nslices = ns; out->padded = padded;
+  out->bytes = padded * (coded ? 4 : kEntB) + ns * 8 + (out->len8 ? nrows : 0);
+  return AMGH_OK;
+}
+// The launch through the sliced-ELL copy where the operator has one: single column only (blocks of right-hand sides, the smoother
+// modes and the stand-alone hooks stay on csr_stream_kernel).  Returns false where the caller launches csr_stream_kernel.
+bool sell_apply(int mode, const StreamArgs& a, const SellCols* sc, hipStream_t st, int ncolv, int* rc) {
+  if (!sc || !sc->w || !g_sell_stream || ncolv != 1 || (!sc->v && !a.vtab)) return false;
+  SellStreamArgs s{};
+  s.w = sc->w; s.v = sc->v; s.slice = sc->slice; s.len = sc->len8; s.rowptr = a.rowptr; s.vtab = a.vtab; s.vtab_n = a.vtab_n;
+  s.nrows = a.row_end; s.nslices = (int32_t)sc->nslices; s.x = a.x; s.b = a.b; s.y = a.y;
+  const dim3 grid((unsigned)((sc->nslices + kThreads / kWave - 1) / (kThreads / kWave))), block(kThreads);
+  const bool coded = sc->v == nullptr;
+  // entries per round: 8 for coded words whose slices average kSellLongSteps steps or more (the 19-entry rows of the second level of 256^3:
+  // 0.241 -> 0.233 ms), else 4 (8 lose on 7-entry rows, 0.216 -> 0.250, and on plain columns + values at any length: profiles/r09_sell_stream.log)
+  const bool b8 = coded && sc->padded >= (int64_t)kSellLongSteps * kWave * sc->nslices;
+#define AMGH_SELL_LAUNCH(M) \
+  do { \
+    if (b8) hipLaunchKernelGGL((sell_stream_kernel<M, true, 8>), grid, block, 0, st, s); \
+    else if (coded) hipLaunchKernelGGL((sell_stream_kernel<M, true, 4>), grid, block, 0, st, s); \
+    else hipLaunchKernelGGL((sell_stream_kernel<M, false, 4>), grid, block, 0, st, s); \
+  } while (0)
+  switch (mode) {
+    case M_SPMV: AMGH_SELL_LAUNCH(M_SPMV); break;
+    case M_RESID: AMGH_SELL_LAUNCH(M_RESID); break;
+    case M_ADD: AMGH_SELL_LAUNCH(M_ADD); break;
+    default: return false;
+  }
+#undef AMGH_SELL_LAUNCH
+  ++const_cast<SellCols*>(sc)->launches;
+  *rc = hipGetLastError() == hipSuccess ? AMGH_OK : -1001;
+  return true;
+}
+
 // ncolv right-hand-side columns (x: ncols apart, y and b: nrows apart) in one launch
+// sell: the caller is one of the cycle's own launches (or a stand-alone operator's): through the operator's sliced-ELL copy where it
+// has one; every other caller (natural-order SpMV of the solvers, residual norms, the stand-alone hooks of a level) stays on csr_stream_kernel
 int csr_apply(const amgh_csr* op, int mode, const real* x, const real* b, real* y, hipStream_t st,
-              int ncolv = 1) {
+              int ncolv = 1, bool sell = false) {
   StreamArgs a{};
   a.rowptr = op->rowptr; a.col = op->col; a.val = op->val;
   a.ccol = op->cc.ccol; a.vtab = op->cc.vtab; a.vtab_n = op->cc.n;
   a.x = x; a.y = y; a.b = b;
   a.row_begin = 0; a.row_end = (int32_t)op->nrows;
   a.ldx = op->ncols; a.ldy = op->nrows; a.ldb = op->nrows;
+  int rc = AMGH_OK;
+  if (sell && sell_apply(mode, a, &op->sc, st, ncolv, &rc)) return rc;
   switch (mode) {
     case M_SPMV: return launch_stream_sized<M_SPMV>(a, st, ncolv, op->xcd_map);
     case M_RESID: return launch_stream_sized<M_RESID>(a, st, ncolv);
@@ -340,13 +415,16 @@ int launch_chain(const ChainArgs& c, bool sor, bool ldsx, int threads, int nx, h
 
 // SpMV-type launch on raw CSR arrays with explicit column strides (operators and vectors in level order)
 int raw_apply(int mode, const int32_t* rowptr, const int32_t* col, const real* val, int64_t nrows, const real* x,
-              int64_t ldx, const real* b, int64_t ldb, real* y, int64_t ldy, hipStream_t st, int ncolv, const CodedCols* cc = nullptr) {
+              int64_t ldx, const real* b, int64_t ldb, real* y, int64_t ldy, hipStream_t st, int ncolv, const CodedCols* cc = nullptr,
+              const SellCols* sc = nullptr) {
   StreamArgs a{};
   a.rowptr = rowptr; a.col = col; a.val = val;
   if (cc) { a.ccol = cc->ccol; a.vtab = cc->vtab; a.vtab_n = cc->n; }
   a.x = x; a.y = y; a.b = b;
   a.row_begin = 0; a.row_end = (int32_t)nrows;
   a.ldx = ldx; a.ldy = ldy; a.ldb = ldb;
+  int rc = AMGH_OK;
+  if (sell_apply(mode, a, sc, st, ncolv, &rc)) return rc;
   switch (mode) {
     case M_SPMV: return launch_stream_sized<M_SPMV>(a, st, ncolv);
     case M_RESID: return launch_stream_sized<M_RESID>(a, st, ncolv);

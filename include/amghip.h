@@ -687,6 +687,26 @@ int amgh_debug_get_tunable(const char* name, int* value);
 int amgh_debug_set_perm_io(int on);
 int amgh_debug_get_perm_io(void);
 int amgh_debug_perm_io_sweeps(int which);
+/* A switch of its own for the sliced-ELL copies of the big operators of a single-column level-ordered cycle (its residual,
+ * restriction and prolongation: one row per lane, entry t of 64 consecutive rows adjacent in memory; bitwise the sums of the
+ * CSR launches).  on (default 1): read at every launch; min_rows (<= 0: 2^18) and cap_pct (<= 0: the compiled-in cap; an
+ * operator takes the layout where its padded entries are at most cap_pct percent of its entries): read at amgh_finalize.
+ * amgh_debug_sell_stream_launches(h, level, which = AMGH_OP_A / AMGH_OP_P / AMGH_OP_R): launches of that operator that went
+ * through the sliced-ELL kernel so far (modulo 2^31; a captured cycle counts when it is captured); -1: no such operator.
+ * amgh_debug_sell_stream_padded: the padded entries of its copy, 0 where none was built.                              */
+int amgh_debug_set_sell_stream(int on, int64_t min_rows, int cap_pct);
+int amgh_debug_get_sell_stream(void);
+int amgh_debug_sell_stream_launches(const amgh_t* h, int level, int which);
+int64_t amgh_debug_sell_stream_padded(const amgh_t* h, int level, int which);
+/* The same copy for a stand-alone operator (tests of the layout itself): built from value-coded words where `coded` and the
+ * operator has at most 256 distinct values, else from its columns and values, under the row threshold and the cap set above;
+ * (the coded words whatever the operator's size).  Returns the padded entries, 0 where the operator does not take the layout,
+ * < 0 on error.  amgh_debug_csr_sell_apply: y = op x (mode 0), y = b - op x (1), y = y + op x (2) on device vectors as the cycle
+ * launches such an operator — through the copy while the switch is on, else csr_stream_kernel; synchronous.  The public
+ * amgh_csr_* entries never read the copy.  amgh_debug_csr_sell_launches: its launches through the sliced-ELL kernel so far.  */
+int64_t amgh_debug_csr_sell(amgh_csr_t* op, int coded);
+int amgh_debug_csr_sell_apply(amgh_csr_t* op, int mode, const amgh_real* x_d, const amgh_real* b_d, amgh_real* y_d);
+int amgh_debug_csr_sell_launches(const amgh_csr_t* op);
 
 /* Replay whole cycles from captured hipGraphs (default off: measured no gain on MI355X for big hierarchies —
  * the cycle is GPU-latency-bound and the host runs far ahead — nor for small ones, whose kernels take >= 3 us each;

@@ -206,6 +206,16 @@ void launch_dma1(const StreamArgs& a, hipStream_t st) {
 }
 #define VA(T, R, E, NT) {"DMA1 T" #T " RPT" #R " EMAX" #E " NT" #NT, launch_dma1<T, R, E, NT>}
 
+// ---- sliced-ELL variants (sell_stream_kernel: one row per lane, entry t of 64 consecutive rows adjacent in memory), built on the
+// host here from the same CSR; plain (columns + values) and value-coded (the matrix's distinct values as a table, one word per entry)
+static SellStreamArgs g_sell[2];   // [0] plain, [1] coded
+template <bool CODED, int B>
+void launch_sell(const StreamArgs& a, hipStream_t st) {
+  SellStreamArgs s = g_sell[CODED ? 1 : 0];
+  s.x = a.x; s.y = a.y;
+  hipLaunchKernelGGL((sell_stream_kernel<M_SPMV, CODED, B>), dim3((s.nslices + 3) / 4), dim3(kThreads), 0, st, s);
+}
+
 #define V(T, R, L, VEC, NT, XCD) {"T" #T " RPT" #R " LDS" #L " VEC" #VEC " NT" #NT " XCD" #XCD, launch_cfg<StreamCfg<T, (T) * (R), L, VEC, NT, XCD>>}
 
 int main(int argc, char** argv) {
@@ -274,6 +284,49 @@ int main(int argc, char** argv) {
     CK(hipFree(d_big));
   }
 
+  // sliced-ELL copies: slices of 64 rows, as many steps as the slice's longest row
+  long sell_padded = 0;
+  bool sell_coded_ok = false;
+  if (!ship_only) {
+    const long ns = (n + 63) / 64;
+    std::vector<uint2> sd(ns);
+    long off = 0;
+    for (long sl = 0; sl < ns; ++sl) {
+      int m = 0;
+      for (long r = sl * 64; r < std::min(n, sl * 64 + 64); ++r) m = std::max(m, rowptr[r + 1] - rowptr[r]);
+      sd[sl] = make_uint2((unsigned)off, (unsigned)m); off += m;
+    }
+    sell_padded = off * 64;
+    std::vector<double> tab(val.begin(), val.end());
+    std::sort(tab.begin(), tab.end()); tab.erase(std::unique(tab.begin(), tab.end()), tab.end());
+    sell_coded_ok = tab.size() <= (size_t)kCodeMax && n <= (1l << kCodeBits);
+    std::vector<uint32_t> wc(sell_padded, 0u), wk(sell_coded_ok ? sell_padded : 0, 0u);
+    std::vector<double> wv(sell_padded, 0.0);
+    std::vector<uint8_t> len8(n);
+    for (long r = 0; r < n; ++r) {
+      const long base = (long)sd[r / 64].x * 64 + r % 64;
+      len8[r] = (uint8_t)(rowptr[r + 1] - rowptr[r]);
+      for (int j = rowptr[r]; j < rowptr[r + 1]; ++j) {
+        const long q = base + (long)(j - rowptr[r]) * 64;
+        wc[q] = (uint32_t)col[j]; wv[q] = val[j];
+        if (sell_coded_ok) wk[q] = (uint32_t)col[j] | ((uint32_t)(std::lower_bound(tab.begin(), tab.end(), val[j]) - tab.begin()) << kCodeBits);
+      }
+    }
+    uint32_t *d_wc, *d_wk = nullptr; double *d_wv, *d_tab = nullptr; uint2* d_sd; uint8_t* d_len;
+    CK(hipMalloc(&d_wc, sell_padded * 4)); CK(hipMalloc(&d_wv, sell_padded * 8)); CK(hipMalloc(&d_sd, ns * 8)); CK(hipMalloc(&d_len, n));
+    CK(hipMemcpy(d_wc, wc.data(), sell_padded * 4, hipMemcpyHostToDevice)); CK(hipMemcpy(d_wv, wv.data(), sell_padded * 8, hipMemcpyHostToDevice));
+    CK(hipMemcpy(d_sd, sd.data(), ns * 8, hipMemcpyHostToDevice)); CK(hipMemcpy(d_len, len8.data(), n, hipMemcpyHostToDevice));
+    if (sell_coded_ok) {
+      CK(hipMalloc(&d_wk, sell_padded * 4)); CK(hipMalloc(&d_tab, kCodeMax * 8));
+      CK(hipMemcpy(d_wk, wk.data(), sell_padded * 4, hipMemcpyHostToDevice)); CK(hipMemcpy(d_tab, tab.data(), tab.size() * 8, hipMemcpyHostToDevice));
+    }
+    SellStreamArgs sa{};
+    sa.slice = d_sd; sa.len = d_len; sa.rowptr = d_rowptr; sa.nrows = (int)n; sa.nslices = (int)ns;
+    g_sell[0] = sa; g_sell[0].w = d_wc; g_sell[0].v = d_wv;
+    g_sell[1] = sa; g_sell[1].w = d_wk; g_sell[1].vtab = d_tab; g_sell[1].vtab_n = (int)tab.size();
+    printf("sliced-ELL: %ld padded entries / %ld (%.3f), %zu distinct values%s\n", sell_padded, nnz, (double)sell_padded / nnz, tab.size(), sell_coded_ok ? "" : " (no coded form)");
+  }
+
   std::vector<Variant> vs = {
       V(256, 2, 4096, 1, false, true),   // round-1 first version
       V(256, 1, 2048, 2, true, true),
@@ -300,6 +353,12 @@ int main(int argc, char** argv) {
       VD(512, 4096, false, 1), VD(512, 4096, false, 2), VD(512, 4096, true, 2),
   };
   if (ship_only) vs = {V(1024, 1, 8192, 4, false, false)};
+  else {
+    vs.push_back({"sliced-ELL plain (12 B / entry) B4", launch_sell<false, 4>});
+    vs.push_back({"sliced-ELL plain (12 B / entry) B8", launch_sell<false, 8>});
+    if (sell_coded_ok) vs.push_back({"sliced-ELL value-coded (4 B / entry) B4", launch_sell<true, 4>});
+    if (sell_coded_ok) vs.push_back({"sliced-ELL value-coded (4 B / entry) B8", launch_sell<true, 8>});
+  }
   StreamArgs a{};
   a.rowptr = d_rowptr; a.col = d_col; a.val = d_val; a.x = d_x; a.y = d_y; a.row_begin = 0; a.row_end = (int)n;
   std::vector<std::vector<float>> times(vs.size() + 1);
